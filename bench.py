@@ -2,7 +2,17 @@
 """bench.py -- BASELINE.json's metric: batched 1-D C2C FFT along the contiguous axis of an
 f64 array, GFFT-points/s (whole job) + achieved HBM GB/s vs the 8 TB/s roofline.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, ramp the clocks and warm up, time ONE block of EXACTLY K steps,
+write the sampled outputs of the last timed step if --dump-outputs is given, print the result line.  Everything else below
+(the median of --blocks blocks, no_ramp, the warm and strong regions, other_configs, host_api, xgmi, cpu_baseline and the numpy
+self-check of the timed outputs) runs only with --full.
+
+--dump-outputs DIR: after the timed steps, a fixed seeded sample of rows of what the last timed step wrote (the array a caller of
+ndfft receives) as DIR/ndfft_out.npy (rank r > 0: ndfft_out_rank<r>.npy), float64 of shape (sampled rows, n, 2) = (re, im), 16 MiB
+over all ranks; the rows are sorted(numpy.random.default_rng(20241008).choice(rows, count, replace=False)).  The timed steps start
+at pair 0 of the rotation, so with the same arguments the last step's input, and thus its output, is the same from run to run.
 
 N > 1 runs N ranks, one per GPU, over torch.distributed (RCCL):
   * under a launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`) the rank
@@ -18,11 +28,11 @@ there is no data-path collective).  One "step" = one ndfft call over one whole r
 Infinity Cache, so every step's input really comes from HBM: this is the HBM-sourced number (round 4; until round 3 the
 headline re-read one 256 MiB input that the Infinity Cache partly holds -- that loop is now `roofline.frac_warm`).
 
-Every region is timed as --blocks (7) blocks of EXACTLY K steps each, every block between barrier + synchronize on both sides,
+With --full, every region is timed as --blocks (7) blocks of EXACTLY K steps each, every block between barrier + synchronize on both sides,
 max over ranks per block; the line reports the MEDIAN block (`steps` = K, `ms_per_step`, `value`) and min / median / max over the
 blocks under `blocks`, so that one ~2 ms sample does not decide the record.
 
-More measurements ride in the same JSON line (each its own timed region, after the primary one):
+With --full, more measurements ride in the same JSON line (each its own timed region, after the primary one):
   * roofline.frac_warm / roofline.warm -- the same call on ONE (in, out) pair re-used every step (Infinity-Cache assisted);
   * strong_cfg5 -- BASELINE configs[4]: the 65536x4096 array split in N contiguous row blocks, one per rank
     (N = 1: the whole 4 GiB + 4 GiB array on one GPU), i.e. STRONG scaling of the north star's multi-GPU target;
@@ -280,7 +290,13 @@ def main():
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--rows", type=int, default=4096, help="lanes per GPU of the primary line (4096 = the metric's shape)")
     ap.add_argument("--cold-pairs", type=int, default=6, help="distinct (in, out) pairs the primary (HBM-sourced) region rotates over (>= 2; 6 pairs = 3 GiB)")
-    ap.add_argument("--blocks", type=int, default=7, help="timed blocks of K steps per region (the line reports the median block and min / median / max)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (median of --blocks blocks, no_ramp, warm, strong_cfg5, other_configs, "
+                         "host_api, xgmi, cpu_baseline, numpy self-check); a plain run times one block of K steps and nothing else")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write a seeded sample of rows of the last timed step's output to DIR/ndfft_out*.npy (float64)")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of K steps per region (the line reports the median block and min / median / max); default 7 with --full, else 1")
     ap.add_argument("--no-warm", action="store_true", help="skip the Infinity-Cache-assisted side measurement (one pair re-used every step)")
     ap.add_argument("--strong-steps", type=int, default=20, help="timed steps of the cfg5 strong-scaling block (0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -296,6 +312,13 @@ def main():
     ap.add_argument("--dry", action="store_true", help="rendezvous + rank count only, no GPU work (CPU test of the launch path)")
     ap.add_argument("--dist", action="store_true", help="initialise torch.distributed (RCCL) even at world size 1 (path check)")
     args = ap.parse_args()
+    if args.profile_phase:                         # the profiled region must run: the others are switched off below
+        args.full = True
+    if args.blocks is None:
+        args.blocks = 7 if args.full else 1
+    if not args.full:                              # a plain run: the headline region and nothing else
+        args.no_no_ramp = args.no_warm = args.no_other_configs = args.no_host_api = args.no_xgmi = args.no_cpu_baseline = True
+        args.strong_steps = 0
     primary_steps = args.steps
     primary_blocks = warm_blocks = max(1, args.blocks)
     args.cold_pairs = max(2, args.cold_pairs)
@@ -464,15 +487,25 @@ def main():
         settled = len(hist) >= 3 and max(hist[-3:]) <= 1.01 * min(hist[-3:])
         if (ramped_ms >= args.ramp_ms and settled) or ramped_ms >= max(3000.0, args.ramp_ms):
             break
+    counter[0] = 0                                 # the ramp's length varies: restart the rotation so that every timed step's pair is fixed by the arguments
     for _ in range(max(args.warmup, 2 * len(pairs) if not args.profile_phase or args.profile_phase == "primary" else 1)):
         step()
     (el, dev_ms), blocks = timed_blocks(step, primary_steps, primary_blocks)
     path = lib.last_path()
     policy = lib.last_input_policy()
 
+    # --dump-outputs: a fixed seeded sample of rows of the output of the last timed step (not timed), 16 MiB over all ranks
+    if args.dump_outputs:
+        last_out = pairs[(counter[0] - 1) % len(pairs)][1]
+        count = min(rows, max(1, (16 << 20) // ngpu // (n * 16)))
+        sel = np.sort(np.random.default_rng(20241008).choice(rows, count, replace=False))
+        sample = torch.view_as_real(last_out.index_select(0, torch.from_numpy(sel).to(dev))).cpu().numpy()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ndfft_out.npy" if rank == 0 else f"ndfft_out_rank{rank}.npy"), sample.astype(np.float64))
+
     # quick self-check of the timed outputs on a few lanes against numpy's FFT (not timed; the oracle is only used by
     # the cpu_baseline leg below and by the tests): pair 0 and the last pair
-    if rank == 0:
+    if rank == 0 and args.full:
         torch.cuda.synchronize()
         for a, b in (pairs[0], pairs[-1]) if primary_steps * primary_blocks + args.warmup >= len(pairs) else (pairs[0],):
             yo = np.fft.fft(a[:4].cpu().numpy(), axis=1)

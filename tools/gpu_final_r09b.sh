@@ -3,7 +3,7 @@
 # build) and with the config table once.   Usage (GPU box): bash tools/gpu_final_r09b.sh <tag>
 TAG=${1:-r09end}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench exit $?" > $OUT/summary.txt
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench exit $?" > $OUT/summary.txt
 timeout 1500 python tools/bench_configs.py --steps 50 --preheat-s 10 --repeat 1 --compare profiles/r08/r08p_configs_final_repeat2.jsonl,profiles/r08/r08v_configs_final_repeat2.jsonl,profiles/r08/r08zz_configs_final_repeat2.jsonl,profiles/r09/r09final_configs_final_repeat2.jsonl > $OUT/configs.jsonl 2> $OUT/configs.err; echo "table exit $?" >> $OUT/summary.txt
 grep "^#" $OUT/configs.err > $OUT/configs_compare.txt
 bash tools/prof_bench.sh $TAG/prof_bench pmc > $OUT/prof_bench.log 2>&1

@@ -3,11 +3,12 @@
 # Usage (GPU box): bash tools/pmc_sq.sh <tag>
 TAG=${1:-pmc_sq}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
 i=0
 for C in "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/p$i -- python3 $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --ramp-ms 0 --no-cpu-baseline > $OUT/p$i.log 2>&1
+  timeout 600 rocprofv3 --pmc $C --output-format csv -d $OUT/p$i -- python3 "$ROOT/bench.py" --full --steps 6 --warmup 2 --ramp-ms 0 --no-cpu-baseline > $OUT/p$i.log 2>&1
   echo "pass $i ($C) exit $?"
 done
 cd $GRAFT_REPO_ROOT
