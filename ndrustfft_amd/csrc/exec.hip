@@ -50,6 +50,21 @@ static int kind_of_op(int op) {
     return NDFFT_KIND_DCT;
 }
 
+// kernel op (generic_kernel.h: G_*) and plan slot of an nd* op on a lane of n points
+static int gen_op_of(int op, int n, int *slot) {
+    *slot = CFG_MAIN;
+    switch (op) {
+        case NDFFT_OP_C2C_FWD: return G_C2C_FWD;
+        case NDFFT_OP_C2C_INV: return G_C2C_INV;
+        case NDFFT_OP_R2C: return n % 2 ? G_R2C_ODD : G_R2C_EVEN;
+        case NDFFT_OP_C2R: return n % 2 ? G_C2R_ODD : G_C2R_EVEN;
+        case NDFFT_OP_DCT1: if (n == 1) return G_DCT2_ODD; *slot = CFG_DCT1; return G_DCT1;
+        case NDFFT_OP_DCT2: return n % 2 ? G_DCT2_ODD : G_DCT2_EVEN;
+        case NDFFT_OP_DCT3: return n % 2 ? G_DCT3_ODD : G_DCT3_EVEN;
+        default: *slot = CFG_DCT4; return n % 2 ? G_DCT4_ODD : G_DCT4_EVEN;
+    }
+}
+
 // validation shared by the host and device entry points; fills Problem. Returns 1 for "nothing to do".
 static int prepare(const ndfft_plan *plan, int op, int ndim, const int64_t *shape_in, const int64_t *stride_in,
                    const int64_t *shape_out, const int64_t *stride_out, int axis, int norm, double scale,
@@ -135,20 +150,8 @@ static int dispatch_generic(const Problem &P, const void *d_in, void *d_out, con
     const int n = (int)plan->n;
     GenArgs<T> a;
     memset(&a, 0, sizeof a);
-    int slot = CFG_MAIN, gop = 0;
-    switch (P.op) {
-        case NDFFT_OP_C2C_FWD: gop = G_C2C_FWD; break;
-        case NDFFT_OP_C2C_INV: gop = G_C2C_INV; break;
-        case NDFFT_OP_R2C: gop = n % 2 ? G_R2C_ODD : G_R2C_EVEN; break;
-        case NDFFT_OP_C2R: gop = n % 2 ? G_C2R_ODD : G_C2R_EVEN; break;
-        case NDFFT_OP_DCT1:
-            if (n == 1) { gop = G_DCT2_ODD; }              // y0 = x0/2 + x0/2 = x0 = DCT-II of length 1
-            else { gop = G_DCT1; slot = CFG_DCT1; }
-            break;
-        case NDFFT_OP_DCT2: gop = n % 2 ? G_DCT2_ODD : G_DCT2_EVEN; break;
-        case NDFFT_OP_DCT3: gop = n % 2 ? G_DCT3_ODD : G_DCT3_EVEN; break;
-        default: gop = n % 2 ? G_DCT4_ODD : G_DCT4_EVEN; slot = CFG_DCT4; break;
-    }
+    int slot;
+    const int gop = gen_op_of(P.op, n, &slot);
     const FftConfig &c = plan->cfg[slot];
     const DevConfig &d = dt.cfg[slot];
     a.in = d_in; a.out = d_out;
@@ -394,6 +397,17 @@ static int get_scratch(int which, hipStream_t s, size_t bytes, void **out) {
 
 static int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t stream);
 
+// A route of dispatch() returns NDFFT_OK, a real error (returned to the caller), or kDeclined: "not mine, the next route runs".
+// kDeclined is no ndfft status and never leaves dispatch().
+constexpr int kDeclined = -1;
+// A hiprtc launcher's NDFFT_ERR_UNSUPPORTED (no hiprtc, a failed compile or module load, NDFFT_JIT=cached with nothing cached) declines its route.
+static int jit_rc(int rc) { return rc == NDFFT_ERR_UNSUPPORTED ? kDeclined : rc; }
+// a route's result: its path is recorded unless it declined
+static int took(int rc, const char *path) {
+    if (rc != kDeclined) set_last_path(path);
+    return rc;
+}
+
 static int transpose_batched(const void *in, void *out, int64_t batch, int64_t rows, int64_t cols, int64_t ld_in, int64_t ld_out,
                              int64_t bs_in, int64_t bs_out, int esz, hipStream_t s) {
     for (int64_t b0 = 0; b0 < batch; b0 += 32768) {   // grid.z limit
@@ -408,7 +422,6 @@ static int transpose_batched(const void *in, void *out, int64_t batch, int64_t r
 
 // Route switches (switches.h; parsed once, never read from the environment on the call path).  Each closes one route so that the kernel
 // behind it runs: the parity tests reach every fallback kernel that way.
-static bool narrow_enabled() { return true; }                              // (long strided lanes on narrow column tiles; the transpose route is the fallback)
 static bool narrow_dct_enabled() { return sw().narrow_dct; }               // NDFFT_NARROW_DCT=1: long strided DCT lanes on the narrow tiles again
 static bool wave_enabled() { return sw().wave; }                           // NDFFT_WAVE=0: short dense C2C lanes on the older kernels
 static bool fourstep2_enabled() { return sw().fourstep2; }                 // NDFFT_FOURSTEP2=0: long power-of-two lanes on the three-pass form
@@ -420,11 +433,30 @@ static int regreal_max_n(int f64) {
     return f64 ? (int)NDFFT_DEV_INT("NDFFT_REGREAL_MAX_F64", 48)           // f64 n = 48: 0.66 vs 0.30
                : (int)NDFFT_DEV_INT("NDFFT_REGREAL_MAX_F32", 72);          // f32 n = 64: 0.66 vs 0.50; n = 96 / 100: 0.39 / 0.37 vs 0.41 / 0.49
 }
-static bool chunk_out_enabled() { return true; }                           // (R2C rows store whole chunks; settled in round 2)
 static bool tiny_enabled() { return sw().tiny; }                           // NDFFT_TINY=0: very short lanes on the LDS kernel
 static bool plain_enabled() { return sw().plain; }                         // NDFFT_PLAIN=0: odd-n real ops with a smooth inner FFT on the LDS kernel
 static bool blue_enabled() { return sw().blue; }                           // NDFFT_BLUE=0: Bluestein lengths on the LDS kernel
 static bool colsplit_enabled() { return sw().colsplit; }                   // NDFFT_COLSPLIT=0: long strided lanes on the narrow-tile / transpose routes
+
+// How one four-step pass of length F runs: on the kernel compiled ahead of time for F (`tables`: the sub-plan has its twiddles), on one
+// specialised with hiprtc (`recipe`: the sub-plan has one, `rtc_ok`: hiprtc can build that kernel), or not at all.
+enum FsPass { FS_NONE = 0, FS_AOT, FS_RTC };
+static FsPass fs_pass(int F, bool tables, bool recipe, bool (*rtc_ok)(int, const JitCfg &), int dtype, const JitCfg &cfg) {
+    if (fourstep_supported(F) && tables) return FS_AOT;
+    return recipe && rtc_ok(dtype, cfg) ? FS_RTC : FS_NONE;
+}
+static bool jit_col_ok(int dtype, const JitCfg &cfg) { return jit_col_lanes(dtype, cfg, false) > 0; }
+template <typename T> static int dtype_of() { return sizeof(T) == 8 ? NDFFT_F64 : NDFFT_F32; }
+
+// RealArgs of a four-step pass: zeroed (the struct's own defaults kept) but for the twiddles W_N^m = twhi[m >> logB] * twlo[m & (2^logB - 1)],
+// N = cs_n, and the lane split (o, k1) = divmod(L / inner, k1n) of pow2_real.h's CS kernels
+template <typename T>
+static RealArgs<T> fs_args(const void *twlo, const void *twhi, int logB, int k1n, int f1, int64_t N) {
+    RealArgs<T> a{};
+    a.cs_twlo = (const cpx<T> *)twlo; a.cs_twhi = (const cpx<T> *)twhi; a.cs_logB = logB;
+    a.cs_k1n = k1n; a.cs_f1 = f1; a.cs_n = (int)N;
+    return a;
+}
 
 // Column four-step (pow2_real.h, CS kernels): a long STRIDED power-of-two lane, n = F1 * F2, as two passes
 // of wide column tiles over a dense C-layout block [O][n][I] -- no transpose, no narrow tiles:
@@ -459,17 +491,11 @@ static int col_split(const Problem &P, const void *d_in, void *d_out, const FftC
         if (C > I) C = I;
     }
     const bool chunked = C < I;
-    // Row pitch of the intermediate.  It is OUR array, so its rows need not sit a power of two apart: tools/colprobe.hip
+    // Row pitch of the intermediate: C, dense rows.  It is OUR array, so its rows need not sit a power of two apart: tools/colprobe.hip
     // (profiles/r05/r05a_colprobe.txt) reads 256-byte segments 8192 rows deep at 0.55 of 8 TB/s when the rows are 32 KiB apart and
     // at 0.85 when they are 32 KiB + 512 B apart (writes 0.33 -> 0.70): a power-of-two pitch keeps every row of a column tile on
-    // the same few HBM channels.  pad_bytes = padding in BYTES (0 keeps dense rows); only for one outer block (the padded
-    // layout needs the (b, i) batch dimensions unmerged, and the column kernels take two).
-    int64_t pad = 0;
-    if (O == 1) {
-        constexpr int pad_bytes = 0;   // measured on cfg3-A / cfg3-A' (profiles/r05/r05a_cs_pad_abab.txt): 0 / 256 / 512 / 1024 B all within 200-207 us: no effect, off
-        pad = pad_bytes / (int64_t)sizeof(cpx<T>);
-    }
-    const int64_t Cp = C + pad;              // pitch of one (k1, b) row of the intermediate, in complex elements
+    // the same few HBM channels.  But padded rows measured on cfg3-A / cfg3-A' (profiles/r05/r05a_cs_pad_abab.txt): 0 / 256 / 512 / 1024 B all within 200-207 us: no effect, off
+    const int64_t Cp = C;                    // pitch of one (k1, b) row of the intermediate, in complex elements
     void *S;
     int rc = get_scratch(5, stream, (size_t)O * K1 * F2 * Cp * sizeof(cpx<T>), &S);
     if (rc) return rc;
@@ -480,23 +506,21 @@ static int col_split(const Problem &P, const void *d_in, void *d_out, const FftC
         const int64_t Cc = std::min(C, I - c0);
         const char *in_c = (const char *)d_in + (size_t)c0 * ein;
         char *out_c = (char *)d_out + (size_t)c0 * eout;
-        RealArgs<T> a;
-        a.nlanes = O * K1 * Cc; a.pitch_in = 0; a.pitch_out = 0; a.vec_in = 0; a.vec_out = 0; a.xcd_remap = 0; a.keep_out = 0;
+        RealArgs<T> a = fs_args<T>(d.cs_twlo, d.cs_twhi, c.cs_logB, K1, F1, P.plan->n);
+        a.nlanes = O * K1 * Cc;
         a.n = F2; a.F = F2; a.n_in = F2; a.n_out = F2; a.scale = (T)P.scale;
-        a.aux1 = nullptr; a.aux2 = nullptr; a.twp = (const cpx<T> *)dt2->cfg[CFG_MAIN].twp_col;
+        a.twp = (const cpx<T> *)dt2->cfg[CFG_MAIN].twp_col;
         a.inner = Cc;
-        a.cs_twlo = (const cpx<T> *)d.cs_twlo; a.cs_twhi = (const cpx<T> *)d.cs_twhi; a.cs_logB = c.cs_logB;
-        a.cs_k1n = K1; a.cs_f1 = F1; a.cs_n = (int)P.plan->n; a.cs_outer_in = sin_o; a.cs_outer_out = sout_o; a.cs_pitch = I;
+        a.cs_outer_in = sin_o; a.cs_outer_out = sout_o; a.cs_pitch = I;
         Problem Q;
         Q.plan = c.cs_sub1; Q.nlanes = O * F2 * Cc; Q.scale = 1.0; Q.no_xcd_map = 1;
-        const bool split_bi = chunked || pad > 0;   // (b, i) as two batch dimensions: the intermediate's rows are not back to back
         if (!c2r) {
             // A: column transform of length F1 over a = row / F2; lanes (b, i)
             Q.op = P.op; Q.xlen = F1; Q.ylen = K1; Q.xs = (int64_t)F2 * I; Q.ys = (int64_t)F2 * Cp;
             // (stream_in: the caller's array is read once and must not push the intermediate out of the Infinity Cache -- round 5, A-B-A-B on cfg3-A:
             //  198-201 -> 188.5-191 us; the C2R form's first stage below: 225 -> 220 us; profiles/r08/r08r_cs_stage_nt_abab.txt)
             Q.keep_out = chunked; Q.stream_in = (int)NDFFT_DEV_INT("NDFFT_CSA_NT", 1);
-            if (split_bi) { Q.b.push_back({(int64_t)F2, I, Cp}); Q.b.push_back({Cc, 1, 1}); }
+            if (chunked) { Q.b.push_back({(int64_t)F2, I, Cp}); Q.b.push_back({Cc, 1, 1}); }   // (b, i) as two batch dimensions: the intermediate's rows are not back to back
             else {
                 if (O > 1) Q.b.push_back({O, sin_o, (int64_t)K1 * F2 * I});
                 Q.b.push_back({(int64_t)F2 * I, 1, 1});
@@ -515,7 +539,7 @@ static int col_split(const Problem &P, const void *d_in, void *d_out, const FftC
             a.stream_in = 0;
             // B: column C2R of length F1 over k1
             Q.op = NDFFT_OP_C2R; Q.xlen = K1; Q.ylen = F1; Q.xs = (int64_t)F2 * Cp; Q.ys = (int64_t)F2 * I;
-            if (split_bi) { Q.b.push_back({(int64_t)F2, Cp, I}); Q.b.push_back({Cc, 1, 1}); }
+            if (chunked) { Q.b.push_back({(int64_t)F2, Cp, I}); Q.b.push_back({Cc, 1, 1}); }
             else {
                 if (O > 1) Q.b.push_back({O, (int64_t)K1 * F2 * I, sout_o});
                 Q.b.push_back({(int64_t)F2 * I, 1, 1});
@@ -570,36 +594,36 @@ static int big_fft(const FftConfig &c, const DevConfig &d, const cpx<T> *zin, in
     //   (2) length-F2 FFTs over n2 of s1 (stride F1, adjacent k1 contiguous), twiddle W_F^(n2 k1) on load, stored at
     //       k1 + F1 k2 = natural order.   256 x 65536 c128: 317 us (three passes) -> see DESIGN.md section 3.5
     // (round 6: a smooth NON-power-of-two factor runs the same two passes on kernels specialised with hiprtc -- jit.hip: launch_jit_fourstep -- instead of the six-pass transpose route)
-    const int dti = sizeof(T) == 8 ? NDFFT_F64 : NDFFT_F32;
+    const int dti = dtype_of<T>();
     const FftConfig &sc1 = c.sub1->cfg[CFG_MAIN], &sc2 = c.sub2->cfg[CFG_MAIN];
-    const int kind1 = (fourstep_supported(F1) && !sc1.twp_col.re.empty()) ? 1 : (sc1.fs_jit && jit_fourstep_ok(dti, sc1.fs_jitcfg)) ? 2 : 0;
-    const int kind2 = (fourstep_supported(F2) && !sc2.twp_col.re.empty()) ? 1 : (sc2.fs_jit && jit_fourstep_ok(dti, sc2.fs_jitcfg)) ? 2 : 0;
+    const FsPass kind1 = fs_pass(F1, !sc1.twp_col.re.empty(), sc1.fs_jit, jit_fourstep_ok, dti, sc1.fs_jitcfg);
+    const FsPass kind2 = fs_pass(F2, !sc2.twp_col.re.empty(), sc2.fs_jit, jit_fourstep_ok, dti, sc2.fs_jitcfg);
+    // (a declined hiprtc pass falls through to the forms below: only the scratch s1 has been written, zout is untouched)
     if (kind1 && kind2 && fourstep2_enabled()) {
         const DevTables *dt1, *dt2;
         if ((rc = get_dev_tables(c.sub1, &dt1)) || (rc = get_dev_tables(c.sub2, &dt2))) return rc;
-        RealArgs<T> a;
-        a.pitch_in = 0; a.vec_in = 0; a.vec_out = 0; a.xcd_remap = 0; a.keep_out = 0; a.stream_in = 0;
-        a.aux1 = nullptr; a.aux2 = nullptr; a.chirp = nullptr; a.bhat = nullptr;
-        a.cs_twlo = (const cpx<T> *)d.twlo; a.cs_twhi = (const cpx<T> *)d.twhi; a.cs_logB = c.logB;
-        a.cs_k1n = 1; a.cs_f1 = F1; a.cs_n = (int)F; a.cs_outer_in = 0; a.cs_outer_out = 0; a.cs_pitch = 0;
+        RealArgs<T> a = fs_args<T>(d.twlo, d.twhi, c.logB, 1, F1, F);
         // (used by the half-line tiles only, F = 1024 f32 -- pow2_real.h; 32 x 2^20 c64: 403 -> 354 us, profiles/r06)
         a.xcd_chunk = (int)NDFFT_DEV_INT("NDFFT_FS_XCD_CHUNK", 32);
         // pass 1: lanes (l, n2)
         a.in = zin; a.out = s1; a.nlanes = L * F2; a.n = F1; a.F = F1; a.n_in = F1; a.n_out = F1; a.scale = (T)1;
-        a.inner = F2; a.outer_in = pitch_in; a.outer_out = 0; a.elem_in = F2; a.elem_out = 0; a.pitch_out = K1p;
-        const bool w1 = kind1 == 1 && fourstep_wide(dti, 1, F1) && dt1->cfg[CFG_MAIN].twp_col_w, w2 = kind2 == 1 && fourstep_wide(dti, 2, F2) && dt2->cfg[CFG_MAIN].twp_col_w;
-        a.twp = (const cpx<T> *)(kind1 == 2 ? dt1->cfg[CFG_MAIN].twp_fs : w1 ? dt1->cfg[CFG_MAIN].twp_col_w : dt1->cfg[CFG_MAIN].twp_col); a.wide = w1 ? 1 : 0;
+        a.inner = F2; a.outer_in = pitch_in; a.elem_in = F2; a.pitch_out = K1p;
+        const bool w1 = kind1 == FS_AOT && fourstep_wide(dti, 1, F1) && dt1->cfg[CFG_MAIN].twp_col_w, w2 = kind2 == FS_AOT && fourstep_wide(dti, 2, F2) && dt2->cfg[CFG_MAIN].twp_col_w;
+        a.twp = (const cpx<T> *)(kind1 == FS_RTC ? dt1->cfg[CFG_MAIN].twp_fs : w1 ? dt1->cfg[CFG_MAIN].twp_col_w : dt1->cfg[CFG_MAIN].twp_col); a.wide = w1 ? 1 : 0;
         // c128 (the lane-fastest kernels): the caller's array is read once -> streaming loads; the intermediate is re-read by pass 2 -> cache-allocating stores.
         // A-B-A-B (profiles/r08/r08s_fourstep_pass1_policy_abab.txt): 256 x 65536 203 -> 197 us, 16 x 2^20 260 -> 248 us; either one alone is neutral or worse
         // (keep alone: 213 us); c64 (staged kernels) 285 -> 291 us with the streaming loads: off there
         a.stream_in = (int)NDFFT_DEV_INT("NDFFT_FS_P1_NT", sizeof(T) == 8 ? 1 : 0); a.keep_out = (int)NDFFT_DEV_INT("NDFFT_FS_KEEP", sizeof(T) == 8 ? 1 : 0);
-        if ((rc = kind1 == 2 ? launch_jit_fourstep<T>(1, inverse, sc1.fs_jitcfg, a, stream) : launch_fourstep<T>(1, F1, inverse, a, stream))) return rc;
-        a.stream_in = 0; a.keep_out = 0;
-        // pass 2: lanes (l, k1)
-        a.in = s1; a.out = zout; a.nlanes = L * F1; a.n = F2; a.F = F2; a.n_in = F2; a.n_out = F2; a.scale = scale;
-        a.inner = F1; a.outer_in = (int64_t)F2 * K1p; a.outer_out = pitch_out; a.elem_in = K1p; a.elem_out = F1; a.pitch_out = 0;
-        a.twp = (const cpx<T> *)(kind2 == 2 ? dt2->cfg[CFG_MAIN].twp_fs : w2 ? dt2->cfg[CFG_MAIN].twp_col_w : dt2->cfg[CFG_MAIN].twp_col); a.wide = w2 ? 1 : 0;
-        return kind2 == 2 ? launch_jit_fourstep<T>(2, inverse, sc2.fs_jitcfg, a, stream) : launch_fourstep<T>(2, F2, inverse, a, stream);
+        rc = kind1 == FS_RTC ? jit_rc(launch_jit_fourstep<T>(1, inverse, sc1.fs_jitcfg, a, stream)) : launch_fourstep<T>(1, F1, inverse, a, stream);
+        if (rc == NDFFT_OK) {
+            a.stream_in = 0; a.keep_out = 0;
+            // pass 2: lanes (l, k1)
+            a.in = s1; a.out = zout; a.nlanes = L * F1; a.n = F2; a.F = F2; a.n_in = F2; a.n_out = F2; a.scale = scale;
+            a.inner = F1; a.outer_in = (int64_t)F2 * K1p; a.outer_out = pitch_out; a.elem_in = K1p; a.elem_out = F1; a.pitch_out = 0;
+            a.twp = (const cpx<T> *)(kind2 == FS_RTC ? dt2->cfg[CFG_MAIN].twp_fs : w2 ? dt2->cfg[CFG_MAIN].twp_col_w : dt2->cfg[CFG_MAIN].twp_col); a.wide = w2 ? 1 : 0;
+            rc = kind2 == FS_RTC ? jit_rc(launch_jit_fourstep<T>(2, inverse, sc2.fs_jitcfg, a, stream)) : launch_fourstep<T>(2, F2, inverse, a, stream);
+        }
+        if (rc != kDeclined) return rc;
     }
     if ((rc = get_scratch(3, stream, (size_t)(L * F) * esz, &s2))) return rc;
     // Fused three-pass form when both halves run on the register kernels:
@@ -611,7 +635,7 @@ static int big_fft(const FftConfig &c, const DevConfig &d, const cpx<T> *zin, in
         const int col_lanes = std::is_same<T, float>::value ? pow2_real_col_lanes<float>(F1, 0) : pow2_real_col_lanes<double>(F1, 0);
         const int nar_lanes = std::is_same<T, float>::value ? pow2_real_narrow_lanes<float>(F1) : pow2_real_narrow_lanes<double>(F1);
         const bool col1 = !c.sub1->cfg[CFG_MAIN].twp_col.re.empty() && F2 >= 8 && col_lanes > 0;
-        const bool nar1 = !c.sub1->cfg[CFG_MAIN].twp_narrow.re.empty() && F2 >= 64 && nar_lanes > 0 && narrow_enabled();
+        const bool nar1 = !c.sub1->cfg[CFG_MAIN].twp_narrow.re.empty() && F2 >= 64 && nar_lanes > 0;
         if (row2 && (col1 || nar1)) {
             Problem Q;
             Q.plan = c.sub1; Q.op = inverse ? NDFFT_OP_C2C_INV : NDFFT_OP_C2C_FWD;
@@ -646,20 +670,6 @@ static int big_fft(const FftConfig &c, const DevConfig &d, const cpx<T> *zin, in
     return transpose_batched(s2, zout, L, F1, F2, F2, F1, F, pitch_out, esz, stream);
 }
 
-static int gen_op_of(int op, int n, int *slot) {
-    *slot = CFG_MAIN;
-    switch (op) {
-        case NDFFT_OP_C2C_FWD: return G_C2C_FWD;
-        case NDFFT_OP_C2C_INV: return G_C2C_INV;
-        case NDFFT_OP_R2C: return n % 2 ? G_R2C_ODD : G_R2C_EVEN;
-        case NDFFT_OP_C2R: return n % 2 ? G_C2R_ODD : G_C2R_EVEN;
-        case NDFFT_OP_DCT1: if (n == 1) return G_DCT2_ODD; *slot = CFG_DCT1; return G_DCT1;
-        case NDFFT_OP_DCT2: return n % 2 ? G_DCT2_ODD : G_DCT2_EVEN;
-        case NDFFT_OP_DCT3: return n % 2 ? G_DCT3_ODD : G_DCT3_EVEN;
-        default: *slot = CFG_DCT4; return n % 2 ? G_DCT4_ODD : G_DCT4_EVEN;
-    }
-}
-
 // REAL four-step for long contiguous real-data lanes, n = N1 * N2 a power of two (plan.hip: add_real_fourstep), R2C and DCT-II:
 //   (1) real FFTs of length N1 over the strided index n1 of x[n1 N2 + n2] (DCT-II: of Makhoul's permutation of x, gathered by the load),
 //       half spectrum stored transposed, s[lane][n2][k1], k1 = 0..N1/2
@@ -678,23 +688,22 @@ static int real_fourstep(const Problem &P, int gop, const FftConfig &c, const De
     const int64_t n = (int64_t)N1 * N2, B = P.nlanes;
     const DevTables *dt1, *dt2;
     int rc;
-    // (round 6: a factor that is not a power of two runs its pass on a kernel specialised with hiprtc -- plan.hip: add_real_fourstep_smooth; NDFFT_ERR_UNSUPPORTED before
+    // (round 6: a factor that is not a power of two runs its pass on a kernel specialised with hiprtc -- plan.hip: add_real_fourstep_smooth; declined before
     //  anything is launched when that is not to be had: the caller falls back to the packed route)
-    const int dti = sizeof(T) == 8 ? NDFFT_F64 : NDFFT_F32;
+    const int dti = dtype_of<T>();
     const FftConfig &rc1 = c.rfs_sub1->cfg[CFG_MAIN], &rc2 = c.rfs_sub2->cfg[CFG_MAIN];
-    const bool jit1 = !fourstep_supported(N1 / 2), jit2 = !fourstep_supported(N2);
-    if ((jit1 && !(rc1.jit && jit_rfs1_ok(dti, rc1.jitcfg))) || (jit2 && !(rc2.fs_jit && jit_fourstep_ok(dti, rc2.fs_jitcfg)))) return NDFFT_ERR_UNSUPPORTED;
+    const FsPass p1 = fs_pass(N1 / 2, true, rc1.jit, jit_rfs1_ok, dti, rc1.jitcfg);
+    if (!p1) return kDeclined;
+    const FsPass p2 = fs_pass(N2, true, rc2.fs_jit, jit_fourstep_ok, dti, rc2.fs_jitcfg);
+    if (!p2) return kDeclined;
+    const bool jit1 = p1 == FS_RTC, jit2 = p2 == FS_RTC;
     if ((rc = get_dev_tables(c.rfs_sub1, &dt1)) || (rc = get_dev_tables(c.rfs_sub2, &dt2))) return rc;
     void *s1;
     if ((rc = get_scratch(4, stream, (size_t)(B * N2 * K) * sizeof(cpx<T>), &s1))) return rc;
-    RealArgs<T> a;
-    a.pitch_in = 0; a.vec_in = 0; a.vec_out = 0; a.xcd_remap = 0; a.keep_out = 0; a.stream_in = 0; a.chunk_out = 0;
-    a.aux2 = nullptr; a.chirp = nullptr; a.bhat = nullptr;
-    a.cs_twlo = (const cpx<T> *)d.rfs_twlo; a.cs_twhi = (const cpx<T> *)d.rfs_twhi; a.cs_logB = c.rfs_logB;
-    a.cs_k1n = 1; a.cs_f1 = N1; a.cs_n = (int)n; a.cs_outer_in = 0; a.cs_outer_out = 0; a.cs_pitch = 0;
+    RealArgs<T> a = fs_args<T>(d.rfs_twlo, d.rfs_twhi, c.rfs_logB, 1, N1, n);
     // pass 1: lanes (l, n2), real input
     a.in = d_in; a.out = s1; a.nlanes = B * N2; a.n = N1; a.F = N1 / 2; a.n_in = N1; a.n_out = N1 / 2 + 1; a.scale = (T)1;
-    a.inner = N2; a.outer_in = pin; a.outer_out = 0; a.elem_in = N2; a.elem_out = 0; a.pitch_out = K;
+    a.inner = N2; a.outer_in = pin; a.elem_in = N2; a.pitch_out = K;
     a.aux1 = (const cpx<T> *)dt1->cfg[CFG_MAIN].aux1; a.twp = (const cpx<T> *)dt1->cfg[CFG_MAIN].twp;
     a.makhoul = gop == G_DCT2_EVEN ? 1 : dct1 ? 3 : 0;
     // streaming loads of the caller's lane in pass 1: R2C re-read 123.5 -> 118 us (HBM-sourced unchanged); not for DCT-II, whose mirror tiles share every line
@@ -708,17 +717,17 @@ static int real_fourstep(const Problem &P, int gop, const FftConfig &c, const De
         const bool resident = row_load_policy(d_in, (size_t)B * (dct1 ? (size_t)(n / 2 + 1) : (size_t)n) * es, d_out, (size_t)B * (size_t)(gop == G_R2C_EVEN ? (n / 2 + 1) * 2 : dct1 ? n / 2 + 1 : n) * es) == 0;
         a.stream_in = (gop == G_DCT2_EVEN || dct1) ? 0 : (knob == 2 ? (resident ? 1 : 0) : (int)knob);     // (DCT-I reads every element twice, through its own tile and the mirrored one)
     }
-    if ((rc = jit1 ? launch_jit_fourstep<T>(11, false, rc1.jitcfg, a, stream) : launch_fourstep_real<T>(1, N1 / 2, a, stream))) return rc;
+    if ((rc = jit1 ? jit_rc(launch_jit_fourstep<T>(11, false, rc1.jitcfg, a, stream)) : launch_fourstep_real<T>(1, N1 / 2, a, stream))) return rc;
     a.stream_in = 0;
     // pass 2: lanes (l, k1)
     a.makhoul = dct1 ? 3 : 0;                        // (3: real outputs Re X[k] a.scale)
     a.keep_out = 1;                                  // plain stores at the lines the mirrored rows share
     a.xcd_chunk = (int)NDFFT_DEV_INT("NDFFT_RFS_XCD_CHUNK", 8);
     a.in = s1; a.out = d_out; a.nlanes = B * K; a.n = N2; a.F = N2; a.n_in = N2; a.n_out = N2; a.scale = dct1 ? (T)(0.5 * P.scale) : (T)P.scale;
-    a.inner = K; a.outer_in = (int64_t)N2 * K; a.outer_out = pout; a.elem_in = K; a.elem_out = 0; a.pitch_out = 0;
+    a.inner = K; a.outer_in = (int64_t)N2 * K; a.outer_out = pout; a.elem_in = K; a.pitch_out = 0;
     a.aux1 = nullptr; a.aux2 = (const cpx<T> *)d.aux2; a.twp = (const cpx<T> *)(jit2 ? dt2->cfg[CFG_MAIN].twp_fs : dt2->cfg[CFG_MAIN].twp_col);
     if (gop == G_DCT2_EVEN && NDFFT_DEV_INT("NDFFT_RFS_FACTORED", 1)) { a.fc1 = (const cpx<T> *)d.rfs_c1; a.fc2 = (const cpx<T> *)d.rfs_c2; }
-    if (jit2) return launch_jit_fourstep<T>(gop == G_DCT2_EVEN ? 13 : 12, false, rc2.fs_jitcfg, a, stream);
+    if (jit2) return jit_rc(launch_jit_fourstep<T>(gop == G_DCT2_EVEN ? 13 : 12, false, rc2.fs_jitcfg, a, stream));
     return launch_fourstep_real<T>(gop == G_DCT2_EVEN ? 3 : 2, N2, a, stream);
 }
 
@@ -735,34 +744,33 @@ static int real_fourstep_inv(const Problem &P, int gop, const FftConfig &c, cons
     const DevTables *dt2;
     int rc;
     // (round 6: N2 not a power of two -> pass 1 on the hiprtc form of the lane-fastest kernel; N1 / 2 not a power of two -> pass 2 through dispatch(): the general column C2R kernel, hiprtc too)
-    const int dti = sizeof(T) == 8 ? NDFFT_F64 : NDFFT_F32;
+    const int dti = dtype_of<T>();
     const FftConfig &rc2 = c.rfs_sub2->cfg[CFG_MAIN];
-    const bool jit2 = !fourstep_supported(N2), aot1 = fourstep_supported(N1 / 2);
-    if (jit2 && !(rc2.fs_jit && jit_rfsi_ok(dti, rc2.fs_jitcfg))) return NDFFT_ERR_UNSUPPORTED;
+    const FsPass p1 = fs_pass(N2, true, rc2.fs_jit, jit_rfsi_ok, dti, rc2.fs_jitcfg);
+    if (!p1) return kDeclined;
+    const bool jit2 = p1 == FS_RTC, aot1 = fourstep_supported(N1 / 2);
     // DCT-III writes its outputs through the inverse of Makhoul's permutation in the LAST pass: only the column-tile kernels do that (RealArgs::makhoul), and dispatch() may
     // pick another kernel for a length that is not a power of two (a small call runs the generic kernel) -- so DCT-III needs the ahead-of-time last pass
     const FftConfig &rc1 = c.rfs_sub1->cfg[CFG_MAIN];
-    const bool jit_last = gop == G_DCT3_EVEN && !aot1;       // ... or the hiprtc column tile of that length, launched HERE (not through dispatch(), which may pick another kernel for a small call)
-    if (jit_last && !(rc1.jit && jit_col_lanes(dti, rc1.jitcfg, false) > 0)) return NDFFT_ERR_UNSUPPORTED;
+    FsPass last = FS_NONE;   // ... or the hiprtc column tile of that length, launched HERE (not through dispatch(), which may pick another kernel for a small call)
+    if (gop == G_DCT3_EVEN && !(last = fs_pass(N1 / 2, true, rc1.jit, jit_col_ok, dti, rc1.jitcfg))) return kDeclined;
+    const bool jit_last = last == FS_RTC;
     if ((rc = get_dev_tables(c.rfs_sub2, &dt2))) return rc;
     void *s1;
     // (no pitch padding here: with + 128 B per row ndifft_r2c 64 x 262144 f64 measured 112 -> 118 us, nddct3 unchanged -- profiles/r08/r08k_longlanes_pad.txt)
     const int64_t N2p = N2;                          // pitch of the intermediate s[k1][n2]
     if ((rc = get_scratch(4, stream, (size_t)(B * Kx * N2p) * sizeof(cpx<T>), &s1))) return rc;
-    RealArgs<T> a;
-    a.pitch_in = 0; a.vec_in = 0; a.vec_out = 0; a.xcd_remap = 0; a.keep_out = 0; a.stream_in = 0; a.chunk_out = 0; a.xcd_chunk = 0; a.makhoul = 0;
-    a.aux1 = nullptr; a.aux2 = (const cpx<T> *)d.aux2; a.chirp = nullptr; a.bhat = nullptr;
-    a.cs_twlo = (const cpx<T> *)d.rfs_twlo; a.cs_twhi = (const cpx<T> *)d.rfs_twhi; a.cs_logB = c.rfs_logB;
-    a.cs_k1n = Kx; a.cs_f1 = N1; a.cs_n = (int)n; a.cs_outer_in = 0; a.cs_outer_out = 0; a.cs_pitch = 0;
+    RealArgs<T> a = fs_args<T>(d.rfs_twlo, d.rfs_twhi, c.rfs_logB, Kx, N1, n);
+    a.aux2 = (const cpx<T> *)d.aux2;
     a.in = d_in; a.out = s1; a.nlanes = B * Kp; a.n = N2; a.F = N2; a.n_in = N2; a.n_out = N2; a.scale = (T)P.scale;
-    a.inner = Kp; a.outer_in = pin; a.outer_out = 0; a.elem_in = N1; a.elem_out = 0; a.pitch_out = N2p;
+    a.inner = Kp; a.outer_in = pin; a.elem_in = N1; a.pitch_out = N2p;
     a.twp = (const cpx<T> *)(jit2 ? dt2->cfg[CFG_MAIN].twp_fs : dt2->cfg[CFG_MAIN].twp_col);
     // runs of consecutive tiles per XCD: the mirrored index N1 - k1 is shifted by one element against the tile grid (and DCT-III's real rows are
     // half lines), so neighbouring tiles share every line
     a.xcd_chunk = (int)NDFFT_DEV_INT("NDFFT_RFS_XCD_CHUNK", 8);
     a.stream_in = (int)NDFFT_DEV_INT("NDFFT_RFSI_P1_NT", 0);      // (measured: ndifft_r2c re-read 112 -> 125 us with streaming loads of the half spectrum: off)
     if (gop == G_DCT3_EVEN && NDFFT_DEV_INT("NDFFT_RFS_FACTORED", 1)) { a.fc1 = (const cpx<T> *)d.rfs_c1; a.fc2 = (const cpx<T> *)d.rfs_c2; }
-    if ((rc = jit2 ? launch_jit_fourstep<T>(gop == G_DCT3_EVEN ? 15 : 14, false, rc2.fs_jitcfg, a, stream) : launch_fourstep_real<T>(gop == G_DCT3_EVEN ? 5 : 4, N2, a, stream))) return rc;
+    if ((rc = jit2 ? jit_rc(launch_jit_fourstep<T>(gop == G_DCT3_EVEN ? 15 : 14, false, rc2.fs_jitcfg, a, stream)) : launch_fourstep_real<T>(gop == G_DCT3_EVEN ? 5 : 4, N2, a, stream))) return rc;
     a.stream_in = 0;
     if ((sw().rfs_c2r_tile && aot1) || jit_last) {   // the column C2R kernel on 128-byte tiles (0: the general column kernel through dispatch())
         const DevTables *dt1;
@@ -772,7 +780,7 @@ static int real_fourstep_inv(const Problem &P, int gop, const FftConfig &c, cons
         a.inner = N2; a.outer_in = (int64_t)Kx * N2p; a.outer_out = pout; a.elem_in = N2p; a.elem_out = N2; a.pitch_in = 0; a.pitch_out = 0;
         a.aux1 = (const cpx<T> *)dt1->cfg[CFG_MAIN].aux1; a.twp = (const cpx<T> *)dt1->cfg[CFG_MAIN].twp;
         a.makhoul = gop == G_DCT3_EVEN ? 1 : 0;
-        if (jit_last) return launch_jit_real<T>(G_C2R_EVEN, rc1.jitcfg, true, a, stream);
+        if (jit_last) return jit_rc(launch_jit_real<T>(G_C2R_EVEN, rc1.jitcfg, true, a, stream));
         return launch_fourstep_real<T>(7, N1 / 2, a, stream);
     }
     Problem Q;
@@ -795,26 +803,23 @@ static int dct4_fourstep(const Problem &P, const FftConfig &c, const DevConfig &
     void *s1;
     const int64_t K1p = F1 + fs_pad_elems<T>();      // pitch of the intermediate s1[n2][k1] (fs_pad_elems)
     if ((rc = get_scratch(2, stream, (size_t)(B * F2 * K1p) * sizeof(cpx<T>), &s1))) return rc;
-    RealArgs<T> a;
-    a.pitch_in = 0; a.vec_in = 0; a.vec_out = 0; a.xcd_remap = 0; a.keep_out = 1; a.stream_in = 0; a.chunk_out = 0; a.xcd_chunk = 0;
-    a.aux1 = (const cpx<T> *)d.aux1; a.aux2 = (const cpx<T> *)d.aux2; a.chirp = nullptr; a.bhat = nullptr;
-    a.cs_twlo = (const cpx<T> *)d.twlo; a.cs_twhi = (const cpx<T> *)d.twhi; a.cs_logB = c.logB;
-    a.cs_k1n = 1; a.cs_f1 = F1; a.cs_n = (int)(2 * F); a.cs_outer_in = 0; a.cs_outer_out = 0; a.cs_pitch = 0;
+    RealArgs<T> a = fs_args<T>(d.twlo, d.twhi, c.logB, 1, F1, 2 * F);
+    a.aux1 = (const cpx<T> *)d.aux1; a.aux2 = (const cpx<T> *)d.aux2;
     // pass 1: lanes (l, n2) of the REAL input
     a.in = d_in; a.out = s1; a.nlanes = B * F2; a.n = F1; a.F = F1; a.n_in = F1; a.n_out = F1; a.scale = (T)P.scale;
-    a.inner = F2; a.outer_in = pin; a.outer_out = 0; a.elem_in = F2; a.elem_out = 0; a.pitch_out = K1p;
+    a.inner = F2; a.outer_in = pin; a.elem_in = F2; a.pitch_out = K1p;
     a.twp = (const cpx<T> *)(jit1 ? dt1->cfg[CFG_MAIN].twp_fs : dt1->cfg[CFG_MAIN].twp_col); a.makhoul = 2;
     // pass 1: streaming loads of the caller's lane, cache-allocating stores of the intermediate (the staged ROWOUT store ignored keep_out until round 5):
     // nddct4 64 x 262144 f64 157.6 -> 153.3 (stores) -> 148-150 us (both)
     a.stream_in = (int)NDFFT_DEV_INT("NDFFT_DCT4_P1_NT", 1); a.keep_out = (int)NDFFT_DEV_INT("NDFFT_DCT4_KEEP", 1);
-    if ((rc = jit1 ? launch_jit_fourstep<T>(1, false, c.sub1->cfg[CFG_MAIN].fs_jitcfg, a, stream) : launch_fourstep<T>(1, F1, false, a, stream))) return rc;
+    if ((rc = jit1 ? jit_rc(launch_jit_fourstep<T>(1, false, c.sub1->cfg[CFG_MAIN].fs_jitcfg, a, stream)) : launch_fourstep<T>(1, F1, false, a, stream))) return rc;
     a.stream_in = 0;
     // pass 2: lanes (l, k1), real output
     a.makhoul = 0; a.keep_out = 0;
     a.in = s1; a.out = d_out; a.nlanes = B * F1; a.n = F2; a.F = F2; a.n_in = F2; a.n_out = F2; a.scale = (T)1;
     a.inner = F1; a.outer_in = (int64_t)F2 * K1p; a.outer_out = pout; a.elem_in = K1p; a.elem_out = 0; a.pitch_out = 0;
     a.twp = (const cpx<T> *)(jit2 ? dt2->cfg[CFG_MAIN].twp_fs : dt2->cfg[CFG_MAIN].twp_col);
-    if (jit2) return launch_jit_fourstep<T>(16, false, c.sub2->cfg[CFG_MAIN].fs_jitcfg, a, stream);
+    if (jit2) return jit_rc(launch_jit_fourstep<T>(16, false, c.sub2->cfg[CFG_MAIN].fs_jitcfg, a, stream));
     return launch_fourstep_real<T>(6, F2, a, stream);
 }
 
@@ -832,36 +837,33 @@ static int dispatch_big(const Problem &P, const void *d_in, void *d_out, const D
         set_last_path(c.bigblue ? "blue_global" : "four_step");
         return rc0;
     }
-    // (a plan whose factors are not powers of two has the forward ops only, and its passes need hiprtc: NDFFT_ERR_UNSUPPORTED from real_fourstep = nothing launched, packed route below)
+    // (a plan whose factors are not powers of two has the forward ops only, and its passes need hiprtc: real_fourstep declines before anything is launched
+    //  when that is not to be had -> packed route below)
     const bool rfs_smooth = c.rfs && (((c.rfs_N1 & (c.rfs_N1 - 1)) != 0) || ((c.rfs_N2 & (c.rfs_N2 - 1)) != 0));
     const int rfs_on = real_fourstep_enabled(), rfs_ops = (rfs_on == 2 ? (c.rfs_ops & 16 ? 16 : 15) : (rfs_on ? c.rfs_ops : 0)) & (rfs_smooth ? c.rfs_ops : 31);
-    if (c.rfs && gop == G_DCT1 && (rfs_ops & 16)) {
-        const int rc0 = real_fourstep<T>(P, gop, c, d, d_in, d_out, pin, pout, stream);
-        if (!(rfs_smooth && rc0 == NDFFT_ERR_UNSUPPORTED)) { set_last_path("real_four_step"); return rc0; }
+    int rc = kDeclined;
+    if (c.rfs && ((gop == G_DCT1 && (rfs_ops & 16)) || (gop == G_DCT2_EVEN && (rfs_ops & 4)) || (gop == G_R2C_EVEN && P.scale == 1.0 && (rfs_ops & 1)))) {
+        rc = real_fourstep<T>(P, gop, c, d, d_in, d_out, pin, pout, stream);
+    } else if (gop == G_DCT4_EVEN && rfs_on && c.big && !c.bigblue && fourstep2_enabled()) {
+        // (round 6: a factor that is not a power of two on the hiprtc forms of the same two kernels -- pass 1 the staged ROWOUT kernel, pass 2 the lane-fastest one, whole rounds)
+        const int dti = dtype_of<T>();
+        const FftConfig &s1c = c.sub1->cfg[CFG_MAIN], &s2c = c.sub2->cfg[CFG_MAIN];
+        const FsPass k1 = fs_pass(c.F1, !s1c.twp_col.re.empty(), s1c.fs_jit, jit_fourstep_ok, dti, s1c.fs_jitcfg);
+        const FsPass k2 = k1 ? fs_pass(c.F2, !s2c.twp_col.re.empty(), s2c.fs_jit, jit_rfsi_ok, dti, s2c.fs_jitcfg) : FS_NONE;
+        if (k2) rc = dct4_fourstep<T>(P, c, d, d_in, d_out, pin, pout, stream, k1 == FS_RTC, k2 == FS_RTC);
+    } else if (c.rfs && ((gop == G_C2R_EVEN && (rfs_ops & 2)) || (gop == G_DCT3_EVEN && (rfs_ops & 8)))) {
+        rc = real_fourstep_inv<T>(P, gop, c, d, d_in, d_out, pin, pout, stream);
     }
-    if (c.rfs && ((gop == G_DCT2_EVEN && (rfs_ops & 4)) || (gop == G_R2C_EVEN && P.scale == 1.0 && (rfs_ops & 1)))) {
-        const int rc0 = real_fourstep<T>(P, gop, c, d, d_in, d_out, pin, pout, stream);
-        if (!(rfs_smooth && rc0 == NDFFT_ERR_UNSUPPORTED)) { set_last_path("real_four_step"); return rc0; }
-    }
-    // (round 6: a factor that is not a power of two on the hiprtc forms of the same two kernels -- pass 1 the staged ROWOUT kernel, pass 2 the lane-fastest one, whole rounds)
-    const int dti4 = sizeof(T) == 8 ? NDFFT_F64 : NDFFT_F32;
-    auto d4_kind1 = [&]() { const FftConfig &s1c = c.sub1->cfg[CFG_MAIN]; return (fourstep_supported(c.F1) && !s1c.twp_col.re.empty()) ? 1 : (s1c.fs_jit && jit_fourstep_ok(dti4, s1c.fs_jitcfg)) ? 2 : 0; };
-    auto d4_kind2 = [&]() { const FftConfig &s2c = c.sub2->cfg[CFG_MAIN]; return (fourstep_supported(c.F2) && !s2c.twp_col.re.empty()) ? 1 : (s2c.fs_jit && jit_rfsi_ok(dti4, s2c.fs_jitcfg)) ? 2 : 0; };
-    if (gop == G_DCT4_EVEN && rfs_on && c.big && !c.bigblue && fourstep2_enabled() && d4_kind1() && d4_kind2()) {
-        const int rc0 = dct4_fourstep<T>(P, c, d, d_in, d_out, pin, pout, stream, d4_kind1() == 2, d4_kind2() == 2);
+    if (rc != kDeclined) {
         set_last_path("real_four_step");
-        return rc0;
+        return rc;
     }
-    if (c.rfs && ((gop == G_C2R_EVEN && (rfs_ops & 2)) || (gop == G_DCT3_EVEN && (rfs_ops & 8)))) {
-        const int rc0 = real_fourstep_inv<T>(P, gop, c, d, d_in, d_out, pin, pout, stream);
-        if (!(rfs_smooth && rc0 == NDFFT_ERR_UNSUPPORTED)) { set_last_path("real_four_step"); return rc0; }
-    }
-    RealArgs<T> a;
+    // packed: PRE pass -> complex four-step of length F -> POST pass
+    RealArgs<T> a{};
     a.in = d_in; a.out = d_out; a.nlanes = P.nlanes; a.pitch_in = pin; a.pitch_out = pout;
     a.n = (int)plan->n; a.F = c.F; a.n_in = (int)P.xlen; a.n_out = (int)P.ylen; a.scale = (T)P.scale;
-    a.aux1 = (const cpx<T> *)d.aux1; a.aux2 = (const cpx<T> *)d.aux2; a.twp = nullptr;
+    a.aux1 = (const cpx<T> *)d.aux1; a.aux2 = (const cpx<T> *)d.aux2;
     void *z;
-    int rc;
     if ((rc = get_scratch(4, stream, (size_t)(P.nlanes * c.F) * sizeof(cpx<T>), &z))) return rc;
     // Two of the ops need only ONE of the elementwise passes over global memory (round 3):
     //   R2C, even n: the PRE fold is z[i] = (x[2i], x[2i+1]) -- the raw real lane read as complex.  The FFT takes the input array itself.
@@ -909,349 +911,339 @@ static int dispatch_transposed(const Problem &P, const void *d_in, void *d_out, 
     return transpose_batched(s2, d_out, outer, inner, n_out, p_out, inner, inner * p_out, n_out * inner, (int)eout, stream);
 }
 
+// The lane layout of one call: lane L = (o, i) with i the fastest batch dimension, element j of it at o * outer + i * lane + j * elem.
+// (dense compares the pitches with the lane lengths xlen / ylen: for C2C both are n)
+struct Layout {
+    bool rows;                       // unit element stride on both sides and one batch dimension at most: lanes at a uniform pitch
+    bool dense;                      // ... and that pitch is the lane length on both sides
+    bool cols;                       // the fastest batch dimension has unit stride on both sides: adjacent lanes are contiguous
+    int64_t pitch_in, pitch_out;     // stride of the slowest batch dimension (the lane pitch of rows), the lane length without one
+    int64_t inner;                   // extent of i (1 without a batch dimension)
+    int64_t lane_in, lane_out;       // stride of i (0 without a batch dimension)
+    int64_t outer_in, outer_out;     // stride of o: the slower of two batch dimensions (0 with fewer)
+    explicit Layout(const Problem &P) {
+        const size_t nb = P.b.size();
+        rows = P.xs == 1 && P.ys == 1 && nb <= 1;
+        pitch_in = nb ? P.b[0].sin : P.xlen; pitch_out = nb ? P.b[0].sout : P.ylen;
+        dense = rows && pitch_in == P.xlen && pitch_out == P.ylen;
+        cols = nb && P.b.back().sin == 1 && P.b.back().sout == 1;
+        inner = nb ? P.b.back().shape : 1;
+        lane_in = nb ? P.b.back().sin : 0; lane_out = nb ? P.b.back().sout : 0;
+        outer_in = nb == 2 ? P.b[0].sin : 0; outer_out = nb == 2 ? P.b[0].sout : 0;
+    }
+};
+
+// one dispatch(): what every route reads
+struct Call {
+    const Problem &P;
+    const void *in; void *out; hipStream_t stream;
+    const ndfft_plan *plan; const DevTables &dt;
+    const Layout L;
+    const int n;                     // handler length
+    int slot, gop;                   // plan slot and kernel op of P.op (gen_op_of)
+    Call(const Problem &P_, const void *in_, void *out_, hipStream_t s, const DevTables &dt_)
+        : P(P_), in(in_), out(out_), stream(s), plan(P_.plan), dt(dt_), L(P_), n((int)P_.plan->n) { gop = gen_op_of(P.op, n, &slot); }
+    bool f32() const { return plan->dtype == NDFFT_F32; }
+};
+
+// short dense power-of-two C2C lanes (n = 2..64): the LDS-free wavefront kernel -- coalesced 16-byte accesses and
+// cross-lane shuffles (wave_kernel.h).  NDFFT_WAVE=0 keeps the older paths (parity tests cover both).
+static int route_wave(const Call &k) {
+    const DevConfig &d = k.dt.cfg[CFG_MAIN];
+    if (!(k.plan->kind == NDFFT_KIND_C2C && wave_supported(k.n) && d.wave_tw && k.L.dense && (uintptr_t)k.in % 16 == 0 &&
+          (uintptr_t)k.out % 16 == 0 && wave_enabled()))
+        return kDeclined;
+    WaveArgs a;
+    a.in = k.in; a.out = k.out; a.total = k.P.nlanes * (int64_t)k.n;
+    a.inverse = k.P.op == NDFFT_OP_C2C_INV; a.scale = k.P.scale; a.tw = d.wave_tw; a.xcd_chunk = 0;
+    set_last_path("wave_reg");
+    return launch_wave(k.plan->dtype, k.n, a, k.stream);
+}
+
+// the arguments of the thread-per-lane kernels (tiny, reg, regreal, tinymat)
+static TinyArgs tiny_args(const Call &k, int inverse, const void *mat) {
+    TinyArgs a;
+    a.in = k.in; a.out = k.out; a.nlanes = k.P.nlanes; a.inverse = inverse; a.scale = k.P.scale; a.mat = mat;
+    a.elem_in = k.P.xs; a.elem_out = k.P.ys;
+    a.inner = k.L.inner; a.lane_in = k.L.lane_in; a.lane_out = k.L.lane_out; a.outer_in = k.L.outer_in; a.outer_out = k.L.outer_out;
+    return a;
+}
+
+// very short C2C lanes (n = 2..13, 16) that the wavefront kernel did not take: one thread per lane (tiny_kernel.h).
+// Column layouts (adjacent lanes contiguous) are coalesced as they are; dense rows are staged through LDS.
+static int route_tiny(const Call &k) {
+    if (!(k.plan->kind == NDFFT_KIND_C2C && tiny_supported(k.n) && k.P.b.size() <= 2 && tiny_enabled())) return kDeclined;
+    const bool stage = k.L.dense;   // 256 lanes x (n | 1) elements of LDS: at most 68 KiB (n = 16, f64)
+    set_last_path(stage ? "tiny_row" : k.L.cols ? "tiny_col" : "tiny_strided");
+    return launch_tiny(k.plan->dtype, k.n, stage, tiny_args(k, k.P.op == NDFFT_OP_C2C_INV, nullptr), k.stream);
+}
+
+// C2C lanes of 14 .. 64 (f64) / 96 (f32) points that factor into two butterflies: one thread per lane, two passes in
+// registers (reg_kernel.h), specialised with hiprtc; only worth a compile when there is real work
+static int route_reg(const Call &k) {
+    const void *mat = k.dt.cfg[CFG_MAIN].wave_tw;
+    int n1, n2;
+    if (!(k.plan->kind == NDFFT_KIND_C2C && k.n >= 14 && k.n <= regfft_max_n(k.plan->dtype) && mat && k.P.b.size() <= 2 &&
+          k.P.nlanes * (int64_t)k.n >= (1 << 16) && tiny_enabled() && !tiny_supported(k.n) && regfft_factor(k.n, &n1, &n2)))
+        return kDeclined;
+    const bool dense = k.L.dense;
+    if (!((dense && k.n <= 63) || (k.L.cols && !dense))) return kDeclined;          // rows beyond 63 points: the general register kernel is faster
+    return took(jit_rc(launch_jit_regfft(k.plan->dtype, n1, n2, dense, tiny_args(k, k.P.op == NDFFT_OP_C2C_INV, mat), k.stream)), dense ? "reg_row" : "reg_col");
+}
+
+// the real-data transforms on lanes of 12 .. 48 (f64) / 72 (f32) points (from 12 up the butterflies beat the dense matrix of the tiny kernel: n = 16 0.49-0.59 -> see DESIGN 3.0c) whose inner FFT factors into butterflies:
+// one thread per lane, everything in registers (reg_kernel.h: RegReal), specialised with hiprtc
+static int route_regreal(const Call &k) {
+    if (!(k.plan->kind != NDFFT_KIND_C2C && k.n >= 12 && k.n <= regreal_max_n(k.f32() ? 0 : 1) && k.P.b.size() <= 2 &&
+          k.P.nlanes * (int64_t)k.n >= (1 << 16) && tiny_enabled()))
+        return kDeclined;
+    const FftConfig &c = k.plan->cfg[k.slot];
+    const DevConfig &d = k.dt.cfg[k.slot];
+    int f1, f2;
+    if (c.big || !d.wave_tw || !regfft_factor(c.F, &f1, &f2) || !(k.L.dense || k.L.cols)) return kDeclined;   // (c.blue does not matter: primes 17..31 have their own butterfly here)
+    RegRealArgs ra;
+    ra.t = tiny_args(k, 0, d.wave_tw); ra.aux1 = d.aux1; ra.aux2 = d.aux2;
+    return took(jit_rc(launch_jit_regreal(k.plan->dtype, k.gop, k.n, f1, f2, k.L.dense, ra, k.stream)), k.L.dense ? "regreal_row" : "regreal_col");
+}
+
+// the real-data transforms on very short lanes (n = 2..16): one thread per lane, the transform as a dense matrix
+static int route_tinymat(const Call &k) {
+    if (!(k.plan->kind != NDFFT_KIND_C2C && k.n >= 2 && k.n <= 16 && k.P.b.size() <= 2 && tiny_enabled())) return kDeclined;
+    const bool r2c = k.plan->kind == NDFFT_KIND_R2C;
+    const int q = r2c ? (k.P.op == NDFFT_OP_R2C ? 0 : 1) : k.P.op - NDFFT_OP_DCT1;
+    const void *mat = k.dt.cfg[CFG_MAIN].tinymat[q];
+    if (!mat) return kDeclined;
+    set_last_path(k.L.dense ? "tinymat_row" : k.L.cols ? "tinymat_col" : "tinymat_strided");
+    const TinyArgs a = tiny_args(k, 0, mat);
+    const int shape = r2c ? q : 2;
+    return k.f32() ? launch_tinymat_f32(k.n, shape, k.L.dense, a, k.stream) : launch_tinymat_f64(k.n, shape, k.L.dense, a, k.stream);
+}
+
+static Pow2Args c2c_row_args(const Call &k) {
+    Pow2Args a;
+    a.in = k.in; a.out = k.out; a.nlanes = k.P.nlanes; a.pitch_in = k.L.pitch_in; a.pitch_out = k.L.pitch_out;
+    a.inverse = k.P.op == NDFFT_OP_C2C_INV; a.scale = k.P.scale; a.twp = k.dt.cfg[CFG_MAIN].twp;
+    return a;
+}
+
+// tuned path: contiguous power-of-two C2C lanes at a uniform pitch
+static int route_pow2_rows(const Call &k) {
+    if (!(k.plan->kind == NDFFT_KIND_C2C && k.plan->cfg[CFG_MAIN].pow2 && k.L.rows)) return kDeclined;
+    Pow2Args a = c2c_row_args(k);
+    if (k.L.dense) a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)k.P.nlanes * k.plan->n * 2 * real_size(k.plan->dtype));
+    set_last_path("pow2_reg");
+    return launch_pow2(k.plan->dtype, k.n, a, k.stream);
+}
+
+// smooth non-power-of-two C2C lanes: the same register-resident kernel, specialised at first use (jit.hip);
+// only worth a compile when there is real work
+static int route_jit_rows(const Call &k) {
+    if (!(k.plan->kind == NDFFT_KIND_C2C && k.plan->cfg[CFG_MAIN].jit && k.L.rows && k.P.nlanes * (int64_t)k.n >= (1 << 17))) return kDeclined;
+    const Pow2Args a = c2c_row_args(k);
+    const size_t bytes_c = (size_t)k.P.nlanes * k.plan->n * 2 * real_size(k.plan->dtype);
+    const int pol = k.L.dense ? c2c_row_load_policy(k.in, k.out, bytes_c) : -1;
+    const int nt = (pol >= 0 ? pol != 0 : stream_loads_for(bytes_c)) ? 3 : 1;
+    const int rc = took(jit_rc(launch_jit_c2c(k.plan->dtype, k.plan->cfg[CFG_MAIN].jitcfg, nt, a, k.stream)), "jit_reg");
+    if (rc == kDeclined && sw().jit_verbose) fprintf(stderr, "ndfft: jit_reg declined n = %zu\n", k.plan->n);   // declined: the LDS kernel
+    return rc;
+}
+
+// which kernel of the register-resident real-op engine (pow2_real.h and its hiprtc forms) a call takes, and where
+struct Engine {
+    bool use_jit, use_rader, use_blue, use_plain, col_alt;
+    bool row, col;
+};
+
+// long strided lanes on XCD-aware narrow column tiles (one HBM pass)
+template <typename T>
+static int narrow_tiles(const Call &k) {
+    const FftConfig &c = k.plan->cfg[k.slot];
+    const DevConfig &d = k.dt.cfg[k.slot];
+    RealArgs<T> a{};
+    a.in = k.in; a.out = k.out; a.nlanes = k.P.nlanes;
+    a.xcd_remap = 1;
+    a.n = k.n; a.F = c.F; a.n_in = (int)k.P.xlen; a.n_out = (int)k.P.ylen; a.scale = (T)k.P.scale;
+    a.inner = k.L.inner; a.outer_in = k.L.outer_in; a.outer_out = k.L.outer_out;
+    a.elem_in = k.P.xs; a.elem_out = k.P.ys;
+    a.aux1 = (const cpx<T> *)d.aux1; a.aux2 = (const cpx<T> *)d.aux2; a.twp = (const cpx<T> *)d.twp_narrow;
+    const int rc = launch_pow2_real_narrow<T>(k.gop, a, k.stream);
+    set_last_path("pow2_col_xcd");
+    return rc;
+}
+
+// rows or column tiles (strategy ii) on the engine
+template <typename T>
+static int engine_tiles(const Call &k, const Engine &e) {
+    const Problem &P = k.P;
+    const FftConfig &c = k.plan->cfg[k.slot];
+    const DevConfig &d = k.dt.cfg[k.slot];
+    const bool col = e.col, is_c2c = k.plan->kind == NDFFT_KIND_C2C;
+    RealArgs<T> a{};
+    a.in = k.in; a.out = k.out; a.nlanes = P.nlanes;
+    a.pitch_in = k.L.pitch_in; a.pitch_out = k.L.pitch_out;
+    a.n = k.n; a.F = c.F; a.n_in = (int)P.xlen; a.n_out = (int)P.ylen; a.scale = (T)P.scale;
+    a.inner = col ? k.L.inner : 1; a.outer_in = col ? k.L.outer_in : 0; a.outer_out = col ? k.L.outer_out : 0;
+    a.elem_in = P.xs; a.elem_out = P.ys;
+    const size_t es_in = (op_in_cplx(P.op) ? 2 : 1) * sizeof(T), es_out = (op_out_cplx(P.op) ? 2 : 1) * sizeof(T);
+    a.vec_in = !col && ((uintptr_t)k.in % 16 == 0) && ((size_t)a.pitch_in * es_in) % 16 == 0;
+    a.keep_out = P.keep_out; a.stream_in = P.stream_in; a.xcd_chunk = P.no_xcd_map ? 0 : -1;
+    a.makhoul = col ? P.makhoul_out : 0;
+    // dense rows of the ahead-of-time real-op kernels (BASELINE configs[3]): load policy from the Infinity-Cache model, as for the C2C rows
+    // (round 5: also the real-input rows of the Rader kernel)
+    if (!col && ((!e.use_jit && !e.use_blue && !e.use_plain) || (e.use_rader && !op_in_cplx(P.op))) && a.pitch_in == P.xlen && a.pitch_out == P.ylen && F_nt_ok(c.F))
+        a.stream_in = row_load_policy(k.in, (size_t)P.nlanes * P.xlen * es_in, k.out, (size_t)P.nlanes * P.ylen * es_out) == 1;
+    // column tiles of a caller's array (not the stages of col_split / the four-step, which set their own policy): the same model
+    if (col && !P.no_xcd_map && !P.stream_in && !P.keep_out)
+        a.stream_in = row_load_policy(k.in, (size_t)P.nlanes * P.xlen * es_in, k.out, (size_t)P.nlanes * P.ylen * es_out) == 1;
+    a.vec_out = !col && ((uintptr_t)k.out % 16 == 0) && ((size_t)a.pitch_out * es_out) % 16 == 0;
+    // R2C rows with dense output lanes: the workgroup stores its lanes as one contiguous chunk (pow2_real.h: chunk_out)
+    // Measured (profiles/r03j, 2^24 points f32): n = 96 / 100 48 -> 37 / 32 -> 30 us, powers of two 128..1024 +4 %; n = 500 / 1000 and
+    // n >= 2048 lose 2-8 % (fewer, longer lanes per workgroup: the per-lane stores are already long runs), so short lanes only.
+    const bool short_lane = c.F <= 64 || (c.F <= 512 && (c.F & (c.F - 1)) == 0);
+    a.chunk_out = !col && k.gop == G_R2C_EVEN && short_lane && ((uintptr_t)k.out % 16 == 0) && a.pitch_out == P.ylen;   // (no switch: settled in round 2)
+    if (a.chunk_out) a.xcd_chunk = 0;
+    a.aux1 = (const cpx<T> *)d.aux1; a.aux2 = (const cpx<T> *)d.aux2; a.twp = (const cpx<T> *)((is_c2c && !e.use_jit && !e.use_blue) ? d.twp_col : d.twp);
+    a.chirp = (const cpx<T> *)d.chirp; a.bhat = (const cpx<T> *)d.bhat; a.twp_rev = (const cpx<T> *)d.twp_rev;
+    if (e.use_rader) {
+        RealArgs<T> r = a;
+        r.twp = (const cpx<T> *)d.rader_twp; r.twp_rev = (const cpx<T> *)d.rader_twp2; r.chirp = (const cpx<T> *)d.rader_ctw; r.bhat = (const cpx<T> *)d.rader_bhat;
+        r.rader_tab = (const int32_t *)d.rader_tab;
+        const int rr = took(jit_rc(launch_jit_rader<T>(k.gop, c.radercfg, col, r, k.stream)), col ? "rader_col" : "rader_reg");
+        if (rr != kDeclined) return rr;
+    }
+    int rc;
+    if (e.use_blue) rc = c.bluereg ? launch_jit_blue<T>(k.gop, c.jitcfg, col, a, k.stream) : NDFFT_ERR_UNSUPPORTED;
+    else if (e.use_plain) rc = launch_jit_plain<T>(k.gop, c.jitcfg, col, a, k.stream);
+    else if (e.use_jit && col && e.col_alt) { a.twp = (const cpx<T> *)d.twp_jcol; rc = launch_jit_real<T>(k.gop, c.jitcfg_col, col, a, k.stream); }
+    else if (e.use_jit) rc = launch_jit_real<T>(k.gop, c.jitcfg, col, a, k.stream);
+    else rc = launch_pow2_real<T>(k.gop, a, col, k.stream);
+    if (e.use_jit || e.use_blue) rc = jit_rc(rc);     // declined: the LDS kernel
+    return took(rc, e.use_blue ? (col ? "blue_col" : "blue_reg") : e.use_plain ? (col ? "plain_col" : "plain_real") : e.use_jit ? (col ? "jit_col" : "jit_real") : (col ? "pow2_col" : "pow2_real"));
+}
+
+// tuned paths on the register-resident real-op engine (pow2_real.h), power-of-two inner FFT:
+//   row: R2C / C2R / DCT on contiguous lanes;  col: the same ops AND C2C on a strided axis whose
+//   adjacent lanes are contiguous (strategy ii), through an LDS tile of adjacent lanes
+// and, for long strided lanes, the column four-step and the narrow tiles
+static int route_real_engine(const Call &k) {
+    const Problem &P = k.P;
+    const ndfft_plan *plan = k.plan;
+    const int gop = k.gop;
+    const FftConfig &c = plan->cfg[k.slot];
+    const DevConfig &d = k.dt.cfg[k.slot];
+    const bool is_c2c = plan->kind == NDFFT_KIND_C2C;
+    const bool odd_variant = gop == G_R2C_ODD || gop == G_C2R_ODD || gop == G_DCT2_ODD || gop == G_DCT3_ODD || gop == G_DCT4_ODD;
+    Engine e;
+    // (2^15 points since round 5: ndfft_r2c axis 0 of the reference's 264 x 264 bench shape is 264 lanes x 132 points -- generic_col 11.6 us, jit_col 6-7 us in a graph;
+    //  its code object ships in jit_prebuilt/)
+    e.use_jit = c.jit && !c.pow2 && P.nlanes * (int64_t)c.F >= (1 << 15);
+    // Bluestein lengths on the register kernel (blue_kernel.h), every op incl. the odd-n variants and row C2C
+    // Rader / Good-Thomas (rader_kernel.h) wherever the plan has a recipe -- also for lanes beyond Bluestein's single-launch reach
+    // (F > 4096: M' = 2^k >= 2F - 1 no longer fits, Rader's F complex elements of LDS do); Bluestein stays the fallback where it exists
+    // (no length rule any more: with the short-lane recipe weights of jit.hip a scan of n = 34..260 has nddct2 on Rader at a median 1.59x over Bluestein with two lengths
+    //  7 % slower, C2C at 1.7x with none, profiles/r04/r04zd_rader_short_real.txt)
+    e.use_rader = c.rader && P.nlanes * (int64_t)c.F >= (1 << 16) && blue_enabled();
+    e.use_blue = e.use_rader || (c.bluereg && ((P.nlanes * (int64_t)c.M >= (1 << 16) && blue_enabled()) || c.blue_reg_only));
+    e.use_plain = odd_variant && e.use_jit && !e.use_blue && plain_enabled();         // odd-n real ops with a smooth inner FFT: plain_kernel.h
+    const bool have_tw = e.use_jit || e.use_blue || (is_c2c ? !c.twp_col.re.empty() : c.pow2);
+    // column tiles of a C2C plan may have their own recipe (FftConfig::jit_col_alt)
+    e.col_alt = e.use_jit && !e.use_blue && !e.use_plain && is_c2c && c.jit_col_alt;
+    const JitCfg &jcol = e.col_alt ? c.jitcfg_col : c.jitcfg;
+    e.row = (!is_c2c || e.use_blue) && k.L.rows;
+    e.col = false;
+    bool narrow = false;
+    const int col_kind = is_c2c ? 0 : (P.op == NDFFT_OP_R2C ? 1 : (P.op == NDFFT_OP_C2R ? 2 : 3));   // which sides of a column tile are real lanes (kernels_pow2_real.hip: ColGeom)
+    if (!e.row && (!odd_variant || e.use_blue || e.use_plain) && P.xlen > 1 && k.L.cols && P.b.size() <= 2) {
+        if (have_tw && k.L.inner >= 8) {
+            const int lanes = (e.use_jit || e.use_blue) ? std::max((e.use_jit || c.bluereg) ? jit_col_lanes(plan->dtype, e.use_blue ? c.jitcfg : jcol, is_c2c && e.use_jit && !e.use_blue) : 0, e.use_rader ? rader_col_lanes(plan->dtype, c.radercfg) : 0)
+                                                    : k.f32() ? pow2_real_col_lanes<float>(c.F, col_kind) : pow2_real_col_lanes<double>(c.F, col_kind);
+            e.col = lanes > 0;
+        }
+        // long lanes: XCD-aware narrow tiles (one HBM pass) instead of the three-pass transpose route (no switch: the transpose route is the fallback)
+        // (not for the DCTs since round 3: transpose -> row kernel -> transpose measured faster -- nddct2 axis 0 of 4096 x 4096 / 8192 x 2048 f32 166 / 172 -> 100 / 103 us,
+        //  f64 174 / 283 -> 164 / 190 us, profiles/r06/r06z_*; C2R f64 n = 4096 stays: 126 vs 174 us)
+        if (!e.col && (col_kind != 3 || narrow_dct_enabled()) && !c.twp_narrow.re.empty() && k.L.inner >= 64) {
+            const int lanes = k.f32() ? pow2_real_narrow_lanes<float>(c.F) : pow2_real_narrow_lanes<double>(c.F);
+            narrow = lanes > 0;
+        }
+    }
+    // long strided power-of-two lanes on a dense C-layout block: column four-step (two wide-tile passes)
+    if (c.cs && k.slot == CFG_MAIN && colsplit_enabled() && !e.row && k.L.cols && P.b.size() <= 2 && P.xs == k.L.inner && P.ys == k.L.inner && k.L.inner >= 16 &&
+        (((P.op == NDFFT_OP_C2C_FWD || P.op == NDFFT_OP_C2C_INV) && (c.cs_ops & 1)) || (P.op == NDFFT_OP_R2C && (c.cs_ops & 2)) || (P.op == NDFFT_OP_C2R && (c.cs_ops & 4))))
+        return k.f32() ? col_split<float>(P, k.in, k.out, c, d, k.stream) : col_split<double>(P, k.in, k.out, c, d, k.stream);
+    if (narrow) return k.f32() ? narrow_tiles<float>(k) : narrow_tiles<double>(k);
+    if (have_tw && (!odd_variant || e.use_blue || e.use_plain) && (e.row || e.col)) return k.f32() ? engine_tiles<float>(k, e) : engine_tiles<double>(k, e);
+    return kDeclined;
+}
+
+// long lanes: four-step on the row kernels (contiguous lanes) -- strided ones reach here via the transpose route
+static int route_long(const Call &k) {
+    if (k.plan->cfg[k.slot].unsupported)
+        return fail(NDFFT_ERR_UNSUPPORTED, "lane length has a prime factor too large for the single-launch Bluestein and no usable "
+                                           "four-step split (DESIGN.md section 9)");
+    if (!(k.plan->cfg[k.slot].big && k.L.rows)) return kDeclined;
+    return k.f32() ? dispatch_big<float>(k.P, k.in, k.out, k.dt, k.stream) : dispatch_big<double>(k.P, k.in, k.out, k.dt, k.stream);
+}
+
+// a route that ran another dispatch() inside: its path is "<prefix><inner path>"
+static int prefixed(const char *prefix, int rc) {
+    if (rc == NDFFT_OK) {
+        static thread_local std::string path;
+        path = std::string(prefix) + last_path();
+        set_last_path(path.c_str());
+    }
+    return rc;
+}
+
+// strided axis of a C-layout array whose lanes are too long for a useful LDS tile of adjacent
+// lanes (< 128 B contiguous per tile row): go through the batched transpose
+static int route_transposed(const Call &k) {
+    const Problem &P = k.P;
+    if (!(P.xs != 1 && P.ys != 1 && P.xlen > 1 && k.L.cols && P.b.size() <= 2)) return kDeclined;
+    const int64_t inner = k.L.inner;
+    const int64_t outer = P.b.size() == 2 ? P.b[0].shape : 1;
+    const size_t r = real_size(k.plan->dtype);
+    const size_t ein = op_in_cplx(P.op) ? 2 * r : r, eout = op_out_cplx(P.op) ? 2 * r : r;
+    const bool c_layout = P.xs == inner && P.ys == inner && (P.b.size() == 1 || (P.b[0].sin == P.xlen * inner && P.b[0].sout == P.ylen * inner));
+    // LDS bytes one lane needs in the generic kernel (two padded complex buffers)
+    const FftConfig &c = k.plan->cfg[k.slot];
+    const size_t per_lane = 2 * (size_t)generic_z_len(std::max(c.blue ? c.M : c.F, 1)) * 2 * r;
+    const size_t fit = c.big ? 0 : (160 * 1024 - 2048) / std::max<size_t>(per_lane, 1);
+    const size_t row_bytes = std::min<size_t>(fit, (size_t)inner) * std::min(ein, eout);
+    if (!(c_layout && row_bytes < 128 && (inner >= 16 || c.big))) return kDeclined;
+    return prefixed("transpose+", dispatch_transposed(P, k.in, k.out, k.stream, outer, inner, ein, eout));
+}
+
+// long lanes in an arbitrary strided layout: pack -> row path on dense lanes -> unpack
+static int route_packed(const Call &k) {
+    const Problem &P = k.P;
+    if (!k.plan->cfg[k.slot].big) return kDeclined;
+    const size_t r = real_size(k.plan->dtype);
+    const size_t ein = op_in_cplx(P.op) ? 2 * r : r, eout = op_out_cplx(P.op) ? 2 * r : r;
+    void *s1, *s2;
+    int rc;
+    if ((rc = get_scratch(0, k.stream, (size_t)(P.nlanes * P.xlen) * ein, &s1))) return rc;
+    if ((rc = get_scratch(1, k.stream, (size_t)(P.nlanes * P.ylen) * eout, &s2))) return rc;
+    LaneGeom gi, go;
+    gi.axis_stride = P.xs; go.axis_stride = P.ys; gi.nb = go.nb = (int32_t)P.b.size(); gi.pad_ = go.pad_ = 0;
+    for (size_t i = 0; i < P.b.size(); ++i) { gi.bshape[i] = go.bshape[i] = P.b[i].shape; gi.bstride[i] = P.b[i].sin; go.bstride[i] = P.b[i].sout; }
+    if ((rc = launch_pack_lanes(k.in, s1, gi, P.nlanes, P.xlen, P.xlen, (int)ein, 0, k.stream))) return rc;
+    Problem Q = P;
+    Q.xs = Q.ys = 1; Q.b.clear(); Q.b.push_back({P.nlanes, P.xlen, P.ylen});
+    if ((rc = dispatch(Q, s1, s2, k.stream))) return rc;
+    return prefixed("pack+", launch_pack_lanes(k.out, s2, go, P.nlanes, P.ylen, P.ylen, (int)eout, 1, k.stream));
+}
+
+// the routes in order of preference; the generic LDS kernel takes whatever none of them does
 static int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t stream) {
     const DevTables *dt;
     int rc = get_dev_tables(P.plan, &dt);
     if (rc) return rc;
-    const ndfft_plan *plan = P.plan;
-    // short dense power-of-two C2C lanes (n = 2..64): the LDS-free wavefront kernel -- coalesced 16-byte accesses and
-    // cross-lane shuffles (wave_kernel.h).  NDFFT_WAVE=0 keeps the older paths (parity tests cover both).
-    if (plan->kind == NDFFT_KIND_C2C && wave_supported((int)plan->n) && dt->cfg[CFG_MAIN].wave_tw && P.xs == 1 && P.ys == 1 && P.b.size() <= 1 &&
-        (P.b.empty() || (P.b[0].sin == (int64_t)plan->n && P.b[0].sout == (int64_t)plan->n)) &&
-        (uintptr_t)d_in % 16 == 0 && (uintptr_t)d_out % 16 == 0 && wave_enabled()) {
-        WaveArgs a;
-        a.in = d_in; a.out = d_out; a.total = P.nlanes * (int64_t)plan->n;
-        a.inverse = P.op == NDFFT_OP_C2C_INV; a.scale = P.scale; a.tw = dt->cfg[CFG_MAIN].wave_tw; a.xcd_chunk = 0;
-        set_last_path("wave_reg");
-        return launch_wave(plan->dtype, (int)plan->n, a, stream);
-    }
-    // very short C2C lanes (n = 2..13, 16) that the wavefront kernel did not take: one thread per lane (tiny_kernel.h).
-    // Column layouts (adjacent lanes contiguous) are coalesced as they are; dense rows are staged through LDS.
-    if (plan->kind == NDFFT_KIND_C2C && tiny_supported((int)plan->n) && P.b.size() <= 2 && tiny_enabled()) {
-        const int n = (int)plan->n;
-        const bool rows = P.xs == 1 && P.ys == 1 && P.b.size() <= 1;
-        const bool dense = rows && (P.b.empty() || (P.b[0].sin == n && P.b[0].sout == n));
-        const bool cols = !P.b.empty() && P.b.back().sin == 1 && P.b.back().sout == 1;
-        {
-            TinyArgs a;
-            a.in = d_in; a.out = d_out; a.nlanes = P.nlanes; a.inverse = P.op == NDFFT_OP_C2C_INV; a.scale = P.scale;
-            a.elem_in = P.xs; a.elem_out = P.ys;
-            a.inner = P.b.empty() ? 1 : P.b.back().shape;
-            a.lane_in = P.b.empty() ? 0 : P.b.back().sin; a.lane_out = P.b.empty() ? 0 : P.b.back().sout;
-            a.outer_in = P.b.size() == 2 ? P.b[0].sin : 0; a.outer_out = P.b.size() == 2 ? P.b[0].sout : 0;
-            const bool stage = dense;   // 256 lanes x (n | 1) elements of LDS: at most 68 KiB (n = 16, f64)
-            set_last_path(stage ? "tiny_row" : cols ? "tiny_col" : "tiny_strided");
-            return launch_tiny(plan->dtype, n, stage, a, stream);
-        }
-    }
-    // C2C lanes of 14 .. 64 (f64) / 96 (f32) points that factor into two butterflies: one thread per lane, two passes in
-    // registers (reg_kernel.h), specialised with hiprtc; only worth a compile when there is real work
-    if (plan->kind == NDFFT_KIND_C2C && plan->n >= 14 && (int)plan->n <= regfft_max_n(plan->dtype) && dt->cfg[CFG_MAIN].wave_tw &&
-        P.b.size() <= 2 && P.nlanes * (int64_t)plan->n >= (1 << 16) && tiny_enabled() && !tiny_supported((int)plan->n)) {
-        int n1, n2;
-        if (regfft_factor((int)plan->n, &n1, &n2)) {
-            const int n = (int)plan->n;
-            const bool rows = P.xs == 1 && P.ys == 1 && P.b.size() <= 1;
-            const bool dense = rows && (P.b.empty() || (P.b[0].sin == n && P.b[0].sout == n));
-            const bool cols = !P.b.empty() && P.b.back().sin == 1 && P.b.back().sout == 1;
-            if ((dense && n <= 63) || (cols && !dense)) {          // rows beyond 63 points: the general register kernel is faster
-                TinyArgs a;
-                a.in = d_in; a.out = d_out; a.nlanes = P.nlanes; a.inverse = P.op == NDFFT_OP_C2C_INV; a.scale = P.scale;
-                a.mat = dt->cfg[CFG_MAIN].wave_tw;
-                a.elem_in = P.xs; a.elem_out = P.ys;
-                a.inner = P.b.empty() ? 1 : P.b.back().shape;
-                a.lane_in = P.b.empty() ? 0 : P.b.back().sin; a.lane_out = P.b.empty() ? 0 : P.b.back().sout;
-                a.outer_in = P.b.size() == 2 ? P.b[0].sin : 0; a.outer_out = P.b.size() == 2 ? P.b[0].sout : 0;
-                const int rcj = launch_jit_regfft(plan->dtype, n1, n2, dense, a, stream);
-                if (rcj == NDFFT_OK) { set_last_path(dense ? "reg_row" : "reg_col"); return NDFFT_OK; }
-                if (rcj != NDFFT_ERR_UNSUPPORTED) return rcj;
-            }
-        }
-    }
-    // the real-data transforms on lanes of 12 .. 48 (f64) / 72 (f32) points (from 12 up the butterflies beat the dense matrix of the tiny kernel: n = 16 0.49-0.59 -> see DESIGN 3.0c) whose inner FFT factors into butterflies:
-    // one thread per lane, everything in registers (reg_kernel.h: RegReal), specialised with hiprtc
-    if (plan->kind != NDFFT_KIND_C2C && plan->n >= 12 && (int)plan->n <= (plan->dtype == NDFFT_F32 ? regreal_max_n(0) : regreal_max_n(1)) &&
-        P.b.size() <= 2 && P.nlanes * (int64_t)plan->n >= (1 << 16) && tiny_enabled()) {
-        const int n = (int)plan->n;
-        int slot;
-        const int gop = gen_op_of(P.op, n, &slot);
-        const FftConfig &c = plan->cfg[slot];
-        const DevConfig &d = dt->cfg[slot];
-        int f1, f2;
-        if (!c.big && d.wave_tw && regfft_factor(c.F, &f1, &f2)) {   // (c.blue does not matter: primes 17..31 have their own butterfly here)
-            const bool rows = P.xs == 1 && P.ys == 1 && P.b.size() <= 1;
-            const bool dense = rows && (P.b.empty() || (P.b[0].sin == P.xlen && P.b[0].sout == P.ylen));
-            const bool cols = !P.b.empty() && P.b.back().sin == 1 && P.b.back().sout == 1;
-            if (dense || cols) {
-                RegRealArgs ra;
-                TinyArgs &a = ra.t;
-                a.in = d_in; a.out = d_out; a.nlanes = P.nlanes; a.inverse = 0; a.scale = P.scale; a.mat = d.wave_tw;
-                a.elem_in = P.xs; a.elem_out = P.ys;
-                a.inner = P.b.empty() ? 1 : P.b.back().shape;
-                a.lane_in = P.b.empty() ? 0 : P.b.back().sin; a.lane_out = P.b.empty() ? 0 : P.b.back().sout;
-                a.outer_in = P.b.size() == 2 ? P.b[0].sin : 0; a.outer_out = P.b.size() == 2 ? P.b[0].sout : 0;
-                ra.aux1 = d.aux1; ra.aux2 = d.aux2;
-                const int rcj = launch_jit_regreal(plan->dtype, gop, n, f1, f2, dense, ra, stream);
-                if (rcj == NDFFT_OK) { set_last_path(dense ? "regreal_row" : "regreal_col"); return NDFFT_OK; }
-                if (rcj != NDFFT_ERR_UNSUPPORTED) return rcj;
-            }
-        }
-    }
-    // the real-data transforms on very short lanes (n = 2..16): one thread per lane, the transform as a dense matrix
-    if (plan->kind != NDFFT_KIND_C2C && plan->n >= 2 && plan->n <= 16 && P.b.size() <= 2 && tiny_enabled()) {
-        const int n = (int)plan->n;
-        const int q = plan->kind == NDFFT_KIND_R2C ? (P.op == NDFFT_OP_R2C ? 0 : 1) : P.op - NDFFT_OP_DCT1;
-        const void *mat = dt->cfg[CFG_MAIN].tinymat[q];
-        if (mat) {
-            const bool rows = P.xs == 1 && P.ys == 1 && P.b.size() <= 1;
-            const bool dense = rows && (P.b.empty() || (P.b[0].sin == P.xlen && P.b[0].sout == P.ylen));
-            const bool cols = !P.b.empty() && P.b.back().sin == 1 && P.b.back().sout == 1;
-            TinyArgs a;
-            a.in = d_in; a.out = d_out; a.nlanes = P.nlanes; a.inverse = 0; a.scale = P.scale; a.mat = mat;
-            a.elem_in = P.xs; a.elem_out = P.ys;
-            a.inner = P.b.empty() ? 1 : P.b.back().shape;
-            a.lane_in = P.b.empty() ? 0 : P.b.back().sin; a.lane_out = P.b.empty() ? 0 : P.b.back().sout;
-            a.outer_in = P.b.size() == 2 ? P.b[0].sin : 0; a.outer_out = P.b.size() == 2 ? P.b[0].sout : 0;
-            set_last_path(dense ? "tinymat_row" : cols ? "tinymat_col" : "tinymat_strided");
-            const int shape = plan->kind == NDFFT_KIND_R2C ? (P.op == NDFFT_OP_R2C ? 0 : 1) : 2;
-            return plan->dtype == NDFFT_F32 ? launch_tinymat_f32(n, shape, dense, a, stream) : launch_tinymat_f64(n, shape, dense, a, stream);
-        }
-    }
-    // tuned path: contiguous power-of-two C2C lanes at a uniform pitch
-    if (plan->kind == NDFFT_KIND_C2C && plan->cfg[CFG_MAIN].pow2 && P.xs == 1 && P.ys == 1 && P.b.size() <= 1) {
-        Pow2Args a;
-        a.in = d_in; a.out = d_out; a.nlanes = P.nlanes;
-        a.pitch_in = P.b.empty() ? (int64_t)plan->n : P.b[0].sin;
-        a.pitch_out = P.b.empty() ? (int64_t)plan->n : P.b[0].sout;
-        a.inverse = P.op == NDFFT_OP_C2C_INV;
-        a.scale = P.scale;
-        a.twp = dt->cfg[CFG_MAIN].twp;
-        if (a.pitch_in == (int64_t)plan->n && a.pitch_out == (int64_t)plan->n)
-            a.stream_in = c2c_row_load_policy(d_in, d_out, (size_t)P.nlanes * plan->n * 2 * real_size(plan->dtype));
-        set_last_path("pow2_reg");
-        return launch_pow2(plan->dtype, (int)plan->n, a, stream);
-    }
-    // smooth non-power-of-two C2C lanes: the same register-resident kernel, specialised at first use (jit.hip);
-    // only worth a compile when there is real work
-    if (plan->kind == NDFFT_KIND_C2C && plan->cfg[CFG_MAIN].jit && P.xs == 1 && P.ys == 1 && P.b.size() <= 1 &&
-        P.nlanes * (int64_t)plan->n >= (1 << 17)) {
-        Pow2Args a;
-        a.in = d_in; a.out = d_out; a.nlanes = P.nlanes;
-        a.pitch_in = P.b.empty() ? (int64_t)plan->n : P.b[0].sin;
-        a.pitch_out = P.b.empty() ? (int64_t)plan->n : P.b[0].sout;
-        a.inverse = P.op == NDFFT_OP_C2C_INV;
-        a.scale = P.scale;
-        a.twp = dt->cfg[CFG_MAIN].twp;
-        const size_t bytes_c = (size_t)P.nlanes * plan->n * 2 * real_size(plan->dtype);
-        const int pol = (a.pitch_in == (int64_t)plan->n && a.pitch_out == (int64_t)plan->n) ? c2c_row_load_policy(d_in, d_out, bytes_c) : -1;
-        const int nt = (pol >= 0 ? pol != 0 : stream_loads_for(bytes_c)) ? 3 : 1;
-        const int rcj = launch_jit_c2c(plan->dtype, plan->cfg[CFG_MAIN].jitcfg, nt, a, stream);
-        if (rcj == NDFFT_OK) { set_last_path("jit_reg"); return NDFFT_OK; }
-        if (rcj != NDFFT_ERR_UNSUPPORTED) return rcj;   // a real HIP error; UNSUPPORTED = no hiprtc / compile failed -> LDS kernel
-        if (sw().jit_verbose) fprintf(stderr, "ndfft: jit_reg declined n = %zu\n", plan->n);
-    }
-    // tuned paths on the register-resident real-op engine (pow2_real.h), power-of-two inner FFT:
-    //   row: R2C / C2R / DCT on contiguous lanes;  col: the same ops AND C2C on a strided axis whose
-    //   adjacent lanes are contiguous (strategy ii), through an LDS tile of adjacent lanes
-    {
-        const int n = (int)plan->n;
-        int slot;
-        const int gop = gen_op_of(P.op, n, &slot);
-        const FftConfig &c = plan->cfg[slot];
-        const DevConfig &d = dt->cfg[slot];
-        const bool is_c2c = plan->kind == NDFFT_KIND_C2C;
-        const bool odd_variant = gop == G_R2C_ODD || gop == G_C2R_ODD || gop == G_DCT2_ODD || gop == G_DCT3_ODD || gop == G_DCT4_ODD;
-        // (2^15 points since round 5: ndfft_r2c axis 0 of the reference's 264 x 264 bench shape is 264 lanes x 132 points -- generic_col 11.6 us, jit_col 6-7 us in a graph;
-        //  its code object ships in jit_prebuilt/)
-        const bool use_jit = c.jit && !c.pow2 && P.nlanes * (int64_t)c.F >= (1 << 15);
-        // Bluestein lengths on the register kernel (blue_kernel.h), every op incl. the odd-n variants and row C2C
-        // Rader / Good-Thomas (rader_kernel.h) wherever the plan has a recipe -- also for lanes beyond Bluestein's single-launch reach
-        // (F > 4096: M' = 2^k >= 2F - 1 no longer fits, Rader's F complex elements of LDS do); Bluestein stays the fallback where it exists
-        // (no length rule any more: with the short-lane recipe weights of jit.hip a scan of n = 34..260 has nddct2 on Rader at a median 1.59x over Bluestein with two lengths
-        //  7 % slower, C2C at 1.7x with none, profiles/r04/r04zd_rader_short_real.txt)
-        const bool use_rader = c.rader && P.nlanes * (int64_t)c.F >= (1 << 16) && blue_enabled();
-        const bool use_blue = use_rader || (c.bluereg && ((P.nlanes * (int64_t)c.M >= (1 << 16) && blue_enabled()) || c.blue_reg_only));
-        const bool use_plain = odd_variant && use_jit && !use_blue && plain_enabled();         // odd-n real ops with a smooth inner FFT: plain_kernel.h
-        const bool have_tw = use_jit || use_blue || (is_c2c ? !c.twp_col.re.empty() : c.pow2);
-        // column tiles of a C2C plan may have their own recipe (FftConfig::jit_col_alt)
-        const bool col_alt = use_jit && !use_blue && !use_plain && is_c2c && c.jit_col_alt;
-        const JitCfg &jcol = col_alt ? c.jitcfg_col : c.jitcfg;
-        const bool row = (!is_c2c || use_blue) && P.xs == 1 && P.ys == 1 && P.b.size() <= 1;
-        bool col = false, narrow = false;
-        const int col_kind = is_c2c ? 0 : (P.op == NDFFT_OP_R2C ? 1 : (P.op == NDFFT_OP_C2R ? 2 : 3));   // which sides of a column tile are real lanes (kernels_pow2_real.hip: ColGeom)
-        if (!row && (!odd_variant || use_blue || use_plain) && P.xlen > 1 && !P.b.empty() && P.b.size() <= 2 && P.b.back().sin == 1 && P.b.back().sout == 1) {
-            if (have_tw && P.b.back().shape >= 8) {
-                const int lanes = (use_jit || use_blue) ? std::max((use_jit || c.bluereg) ? jit_col_lanes(plan->dtype, use_blue ? c.jitcfg : jcol, is_c2c && use_jit && !use_blue) : 0, use_rader ? rader_col_lanes(plan->dtype, c.radercfg) : 0)
-                                          : plan->dtype == NDFFT_F32 ? pow2_real_col_lanes<float>(c.F, col_kind) : pow2_real_col_lanes<double>(c.F, col_kind);
-                col = lanes > 0;
-            }
-            // long lanes: XCD-aware narrow tiles (one HBM pass) instead of the three-pass transpose route
-            // (not for the DCTs since round 3: transpose -> row kernel -> transpose measured faster -- nddct2 axis 0 of 4096 x 4096 / 8192 x 2048 f32 166 / 172 -> 100 / 103 us,
-            //  f64 174 / 283 -> 164 / 190 us, profiles/r06/r06z_*; C2R f64 n = 4096 stays: 126 vs 174 us)
-            if (!col && (col_kind != 3 || narrow_dct_enabled()) && !c.twp_narrow.re.empty() && P.b.back().shape >= 64 && narrow_enabled()) {
-                const int lanes = plan->dtype == NDFFT_F32 ? pow2_real_narrow_lanes<float>(c.F) : pow2_real_narrow_lanes<double>(c.F);
-                narrow = lanes > 0;
-            }
-        }
-        // long strided power-of-two lanes on a dense C-layout block: column four-step (two wide-tile passes)
-        if (c.cs && slot == CFG_MAIN && colsplit_enabled() && !row && !P.b.empty() && P.b.size() <= 2 && P.b.back().sin == 1 &&
-            P.b.back().sout == 1 && P.xs == P.b.back().shape && P.ys == P.b.back().shape && P.b.back().shape >= 16 &&
-            (((P.op == NDFFT_OP_C2C_FWD || P.op == NDFFT_OP_C2C_INV) && (c.cs_ops & 1)) || (P.op == NDFFT_OP_R2C && (c.cs_ops & 2)) || (P.op == NDFFT_OP_C2R && (c.cs_ops & 4)))) {
-            return plan->dtype == NDFFT_F32 ? col_split<float>(P, d_in, d_out, c, d, stream) : col_split<double>(P, d_in, d_out, c, d, stream);
-        }
-        if (narrow) {
-            auto fill = [&](auto &a) {
-                a.in = d_in; a.out = d_out; a.nlanes = P.nlanes;
-                a.pitch_in = 0; a.pitch_out = 0; a.vec_in = 0; a.vec_out = 0;
-                a.xcd_remap = 1;
-                a.keep_out = 0;
-                a.n = n; a.F = c.F; a.n_in = (int)P.xlen; a.n_out = (int)P.ylen;
-                a.inner = P.b.back().shape;
-                a.outer_in = P.b.size() == 2 ? P.b[0].sin : 0;
-                a.outer_out = P.b.size() == 2 ? P.b[0].sout : 0;
-                a.elem_in = P.xs; a.elem_out = P.ys;
-            };
-            int rc2;
-            if (plan->dtype == NDFFT_F32) {
-                RealArgs<float> a; fill(a); a.scale = (float)P.scale;
-                a.aux1 = (const cpx<float> *)d.aux1; a.aux2 = (const cpx<float> *)d.aux2; a.twp = (const cpx<float> *)d.twp_narrow;
-                rc2 = launch_pow2_real_narrow<float>(gop, a, stream);
-            } else {
-                RealArgs<double> a; fill(a); a.scale = P.scale;
-                a.aux1 = (const double2 *)d.aux1; a.aux2 = (const double2 *)d.aux2; a.twp = (const double2 *)d.twp_narrow;
-                rc2 = launch_pow2_real_narrow<double>(gop, a, stream);
-            }
-            set_last_path("pow2_col_xcd");
-            return rc2;
-        }
-        if (have_tw && (!odd_variant || use_blue || use_plain) && (row || col)) {
-            auto fill = [&](auto &a) {
-                a.in = d_in; a.out = d_out; a.nlanes = P.nlanes;
-                a.pitch_in = P.b.empty() ? P.xlen : P.b[0].sin;
-                a.pitch_out = P.b.empty() ? P.ylen : P.b[0].sout;
-                a.n = n; a.F = c.F; a.n_in = (int)P.xlen; a.n_out = (int)P.ylen;
-                a.inner = col ? P.b.back().shape : 1;
-                a.outer_in = col && P.b.size() == 2 ? P.b[0].sin : 0;
-                a.outer_out = col && P.b.size() == 2 ? P.b[0].sout : 0;
-                a.elem_in = P.xs; a.elem_out = P.ys;
-                const size_t es_in = (op_in_cplx(P.op) ? 2 : 1) * real_size(plan->dtype);
-                a.vec_in = !col && ((uintptr_t)d_in % 16 == 0) && ((size_t)a.pitch_in * es_in) % 16 == 0;
-                a.xcd_remap = 0; a.keep_out = P.keep_out; a.stream_in = P.stream_in; a.xcd_chunk = P.no_xcd_map ? 0 : -1;
-                a.makhoul = col ? P.makhoul_out : 0;
-                const size_t es_out = (op_out_cplx(P.op) ? 2 : 1) * real_size(plan->dtype);
-                // dense rows of the ahead-of-time real-op kernels (BASELINE configs[3]): load policy from the Infinity-Cache model, as for the C2C rows
-                // (round 5: also the real-input rows of the Rader kernel)
-                if (!col && ((!use_jit && !use_blue && !use_plain) || (use_rader && !op_in_cplx(P.op))) && a.pitch_in == P.xlen && a.pitch_out == P.ylen && F_nt_ok(c.F))
-                    a.stream_in = row_load_policy(d_in, (size_t)P.nlanes * P.xlen * es_in, d_out, (size_t)P.nlanes * P.ylen * es_out) == 1;
-                // column tiles of a caller's array (not the stages of col_split / the four-step, which set their own policy): the same model
-                if (col && !P.no_xcd_map && !P.stream_in && !P.keep_out)
-                    a.stream_in = row_load_policy(d_in, (size_t)P.nlanes * P.xlen * es_in, d_out, (size_t)P.nlanes * P.ylen * es_out) == 1;
-                a.vec_out = !col && ((uintptr_t)d_out % 16 == 0) && ((size_t)a.pitch_out * es_out) % 16 == 0;
-                // R2C rows with dense output lanes: the workgroup stores its lanes as one contiguous chunk (pow2_real.h: chunk_out)
-                // Measured (profiles/r03j, 2^24 points f32): n = 96 / 100 48 -> 37 / 32 -> 30 us, powers of two 128..1024 +4 %; n = 500 / 1000 and
-                // n >= 2048 lose 2-8 % (fewer, longer lanes per workgroup: the per-lane stores are already long runs), so short lanes only.
-                const bool short_lane = c.F <= 64 || (c.F <= 512 && (c.F & (c.F - 1)) == 0);
-                a.chunk_out = !col && gop == G_R2C_EVEN && short_lane && ((uintptr_t)d_out % 16 == 0) && a.pitch_out == P.ylen && chunk_out_enabled();
-                if (a.chunk_out) a.xcd_chunk = 0;
-            };
-            int rc2;
-            if (plan->dtype == NDFFT_F32) {
-                RealArgs<float> a; fill(a); a.scale = (float)P.scale;
-                a.aux1 = (const cpx<float> *)d.aux1; a.aux2 = (const cpx<float> *)d.aux2; a.twp = (const cpx<float> *)((is_c2c && !use_jit && !use_blue) ? d.twp_col : d.twp);
-                a.chirp = (const cpx<float> *)d.chirp; a.bhat = (const cpx<float> *)d.bhat; a.twp_rev = (const cpx<float> *)d.twp_rev;
-                if (use_rader) {
-                    RealArgs<float> r = a;
-                    r.twp = (const cpx<float> *)d.rader_twp; r.twp_rev = (const cpx<float> *)d.rader_twp2; r.chirp = (const cpx<float> *)d.rader_ctw; r.bhat = (const cpx<float> *)d.rader_bhat; r.rader_tab = (const int32_t *)d.rader_tab;
-                    const int rr = launch_jit_rader<float>(gop, c.radercfg, col, r, stream);
-                    if (rr != NDFFT_ERR_UNSUPPORTED) { set_last_path(col ? "rader_col" : "rader_reg"); return rr; }
-                }
-                rc2 = use_blue ? (c.bluereg ? launch_jit_blue<float>(gop, c.jitcfg, col, a, stream) : NDFFT_ERR_UNSUPPORTED)
-                      : use_plain ? launch_jit_plain<float>(gop, c.jitcfg, col, a, stream)
-                      : use_jit ? ((col && col_alt) ? (a.twp = (const cpx<float> *)d.twp_jcol, launch_jit_real<float>(gop, jcol, col, a, stream)) : launch_jit_real<float>(gop, c.jitcfg, col, a, stream))
-                      : launch_pow2_real<float>(gop, a, col, stream);
-            } else {
-                RealArgs<double> a; fill(a); a.scale = P.scale;
-                a.aux1 = (const double2 *)d.aux1; a.aux2 = (const double2 *)d.aux2; a.twp = (const double2 *)((is_c2c && !use_jit && !use_blue) ? d.twp_col : d.twp);
-                a.chirp = (const double2 *)d.chirp; a.bhat = (const double2 *)d.bhat; a.twp_rev = (const double2 *)d.twp_rev;
-                if (use_rader) {
-                    RealArgs<double> r = a;
-                    r.twp = (const double2 *)d.rader_twp; r.twp_rev = (const double2 *)d.rader_twp2; r.chirp = (const double2 *)d.rader_ctw; r.bhat = (const double2 *)d.rader_bhat; r.rader_tab = (const int32_t *)d.rader_tab;
-                    const int rr = launch_jit_rader<double>(gop, c.radercfg, col, r, stream);
-                    if (rr != NDFFT_ERR_UNSUPPORTED) { set_last_path(col ? "rader_col" : "rader_reg"); return rr; }
-                }
-                rc2 = use_blue ? (c.bluereg ? launch_jit_blue<double>(gop, c.jitcfg, col, a, stream) : NDFFT_ERR_UNSUPPORTED)
-                      : use_plain ? launch_jit_plain<double>(gop, c.jitcfg, col, a, stream)
-                      : use_jit ? ((col && col_alt) ? (a.twp = (const double2 *)d.twp_jcol, launch_jit_real<double>(gop, jcol, col, a, stream)) : launch_jit_real<double>(gop, c.jitcfg, col, a, stream))
-                      : launch_pow2_real<double>(gop, a, col, stream);
-            }
-            if (!((use_jit || use_blue) && rc2 == NDFFT_ERR_UNSUPPORTED)) {   // UNSUPPORTED from the JIT = no hiprtc / compile failed: fall through to the LDS kernel
-                set_last_path(use_blue ? (col ? "blue_col" : "blue_reg") : use_plain ? (col ? "plain_col" : "plain_real") : use_jit ? (col ? "jit_col" : "jit_real") : (col ? "pow2_col" : "pow2_real"));
-                return rc2;
-            }
-        }
-    }
-    {   // long lanes: four-step on the row kernels (contiguous lanes) -- strided ones reach here via the transpose route
-        int slot;
-        (void)gen_op_of(P.op, (int)plan->n, &slot);
-        const FftConfig &c = plan->cfg[slot];
-        if (c.unsupported)
-            return fail(NDFFT_ERR_UNSUPPORTED, "lane length has a prime factor too large for the single-launch Bluestein and no usable "
-                                               "four-step split (DESIGN.md section 9)");
-        if (c.big && P.xs == 1 && P.ys == 1 && P.b.size() <= 1)
-            return plan->dtype == NDFFT_F32 ? dispatch_big<float>(P, d_in, d_out, *dt, stream) : dispatch_big<double>(P, d_in, d_out, *dt, stream);
-    }
-    // strided axis of a C-layout array whose lanes are too long for a useful LDS tile of adjacent
-    // lanes (< 128 B contiguous per tile row): go through the batched transpose
-    if (P.xs != 1 && P.ys != 1 && P.xlen > 1 && !P.b.empty() && P.b.back().sin == 1 && P.b.back().sout == 1 && P.b.size() <= 2) {
-        const int64_t inner = P.b.back().shape;
-        const int64_t outer = P.b.size() == 2 ? P.b[0].shape : 1;
-        const size_t r = real_size(plan->dtype);
-        const size_t ein = op_in_cplx(P.op) ? 2 * r : r, eout = op_out_cplx(P.op) ? 2 * r : r;
-        const bool c_layout = P.xs == inner && P.ys == inner &&
-                              (P.b.size() == 1 || (P.b[0].sin == P.xlen * inner && P.b[0].sout == P.ylen * inner));
-        // LDS bytes one lane needs in the generic kernel (two padded complex buffers)
-        const int slot = P.op == NDFFT_OP_DCT1 && plan->n > 1 ? CFG_DCT1 : P.op == NDFFT_OP_DCT4 ? CFG_DCT4 : CFG_MAIN;
-        const FftConfig &c = plan->cfg[slot];
-        const size_t per_lane = 2 * (size_t)generic_z_len(std::max(c.blue ? c.M : c.F, 1)) * 2 * r;
-        const size_t fit = c.big ? 0 : (160 * 1024 - 2048) / std::max<size_t>(per_lane, 1);
-        const size_t row_bytes = std::min<size_t>(fit, (size_t)inner) * std::min(ein, eout);
-        if (c_layout && row_bytes < 128 && (inner >= 16 || c.big)) {
-            int rc2 = dispatch_transposed(P, d_in, d_out, stream, outer, inner, ein, eout);
-            if (!rc2) {
-                static thread_local std::string path;
-                path = std::string("transpose+") + last_path();
-                set_last_path(path.c_str());
-            }
-            return rc2;
-        }
-    }
-    {
-        int slot;
-        (void)gen_op_of(P.op, (int)plan->n, &slot);
-        if (plan->cfg[slot].big) {
-            // long lanes in an arbitrary strided layout: pack -> row path on dense lanes -> unpack
-            const size_t r = real_size(plan->dtype);
-            const size_t ein = op_in_cplx(P.op) ? 2 * r : r, eout = op_out_cplx(P.op) ? 2 * r : r;
-            void *s1, *s2;
-            int rc2;
-            if ((rc2 = get_scratch(0, stream, (size_t)(P.nlanes * P.xlen) * ein, &s1))) return rc2;
-            if ((rc2 = get_scratch(1, stream, (size_t)(P.nlanes * P.ylen) * eout, &s2))) return rc2;
-            LaneGeom gi, go;
-            gi.axis_stride = P.xs; go.axis_stride = P.ys; gi.nb = go.nb = (int32_t)P.b.size(); gi.pad_ = go.pad_ = 0;
-            for (size_t k = 0; k < P.b.size(); ++k) { gi.bshape[k] = go.bshape[k] = P.b[k].shape; gi.bstride[k] = P.b[k].sin; go.bstride[k] = P.b[k].sout; }
-            if ((rc2 = launch_pack_lanes(d_in, s1, gi, P.nlanes, P.xlen, P.xlen, (int)ein, 0, stream))) return rc2;
-            Problem Q = P;
-            Q.xs = Q.ys = 1; Q.b.clear(); Q.b.push_back({P.nlanes, P.xlen, P.ylen});
-            if ((rc2 = dispatch(Q, s1, s2, stream))) return rc2;
-            if ((rc2 = launch_pack_lanes(d_out, s2, go, P.nlanes, P.ylen, P.ylen, (int)eout, 1, stream))) return rc2;
-            static thread_local std::string path;
-            path = std::string("pack+") + last_path();
-            set_last_path(path.c_str());
-            return NDFFT_OK;
-        }
-    }
-    return plan->dtype == NDFFT_F32 ? dispatch_generic<float>(P, d_in, d_out, *dt, stream)
-                                    : dispatch_generic<double>(P, d_in, d_out, *dt, stream);
+    const Call k(P, d_in, d_out, stream, *dt);
+    for (int (*route)(const Call &) : {route_wave, route_tiny, route_reg, route_regreal, route_tinymat, route_pow2_rows, route_jit_rows,
+                                       route_real_engine, route_long, route_transposed, route_packed})
+        if ((rc = route(k)) != kDeclined) return rc;
+    return k.f32() ? dispatch_generic<float>(P, d_in, d_out, *dt, stream) : dispatch_generic<double>(P, d_in, d_out, *dt, stream);
 }
 
 // more than kMaxBatchDims un-mergeable batch dims: peel the slowest ones on the host

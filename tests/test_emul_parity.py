@@ -328,3 +328,93 @@ def test_sharded_device_resident_fake_devices(L):
         L.check(L.c.ndfft_dev_free(din)); L.check(L.c.ndfft_dev_free(dout))
     finally:
         L.c.ndfft_set_device(0)
+
+
+# (switches, op, shape, axis, dtype, layout) -> last_path(): the route every case took when this table was recorded.  A change to
+# exec.hip's routing that moves any of them shows up here first.
+ROUTE_TABLE = [
+    ({}, "ndfft", (5, 64), 1, np.float64, "C", "wave_reg"),
+    ({"NDFFT_WAVE": "0"}, "ndfft", (37, 64), 1, np.float64, "C", "pow2_reg"),
+    ({"NDFFT_WAVE": "0"}, "ndifft", (37, 16), 1, np.float64, "C", "tiny_row"),
+    ({"NDFFT_WAVE": "0", "NDFFT_TINY": "0"}, "ndifft", (37, 16), 1, np.float64, "C", "generic_row"),
+    ({}, "ndfft", (3, 7, 70), 1, np.float64, "C", "tiny_col"),
+    ({}, "ndfft", (40, 7), 1, np.float32, "F", "tiny_col"),
+    ({}, "ndfft", (3645, 18), 1, np.float64, "C", "reg_row"),
+    ({}, "ndfft", (5, 18, 911), 1, np.float64, "C", "reg_col"),
+    ({}, "nddct2", (3670, 18), 1, np.float64, "C", "regreal_row"),
+    ({}, "ndfft_r2c", (3, 18, 1835), 1, np.float64, "C", "regreal_col"),
+    ({}, "nddct2", (300, 12), 1, np.float64, "C", "tinymat_row"),
+    ({}, "nddct3", (9, 12, 70), 1, np.float32, "C", "tinymat_col"),
+    ({}, "ndifft_r2c", (33, 12), 1, np.float64, "F", "tinymat_col"),
+    ({}, "ndfft", (2, 2048), 1, np.float64, "C", "pow2_reg"),
+    ({}, "ndfft", (503, 264), 1, np.float64, "C", "jit_reg"),
+    ({}, "nddct2", (253, 528), 1, np.float64, "C", "jit_real"),
+    ({}, "ndfft", (264, 256), 0, np.float32, "C", "jit_col"),
+    ({}, "ndfft", (3, 1000), 1, np.float64, "C", "generic_row"),
+    ({}, "ndfft", (1356, 97), 1, np.float64, "C", "rader_reg"),
+    ({}, "ndifft_r2c", (97, 1000), 0, np.float64, "C", "rader_col"),
+    ({"NDFFT_RADER": "0"}, "ndfft", (517, 97), 1, np.float64, "C", "blue_reg"),
+    ({"NDFFT_RADER": "0"}, "ndfft", (97, 520), 0, np.float64, "C", "blue_col"),
+    ({"NDFFT_RADER": "0", "NDFFT_BLUE": "0"}, "ndfft", (517, 97), 1, np.float64, "C", "generic_row"),
+    ({"NDFFT_RADER": "0", "NDFFT_BLUE": "0"}, "ndfft", (97, 40), 0, np.float64, "C", "generic_col"),
+    ({"NDFFT_TINY": "0"}, "nddct2", (2917, 45), 1, np.float64, "C", "plain_real"),
+    ({"NDFFT_TINY": "0"}, "ndfft_r2c", (45, 2920), 0, np.float64, "C", "plain_col"),
+    ({}, "nddct2", (5, 128), 1, np.float64, "C", "pow2_real"),
+    ({}, "ndfft", (64, 40), 0, np.float64, "C", "pow2_col"),
+    ({}, "ndifft_r2c", (3, 256, 17), 1, np.float32, "C", "pow2_col"),
+    ({}, "ndfft", (4096, 16), 0, np.float64, "C", "col_split"),
+    ({}, "ndifft_r2c", (8192, 40), 0, np.float32, "C", "col_split"),
+    ({"NDFFT_COLSPLIT": "0"}, "ndfft", (4096, 64), 0, np.float64, "C", "pow2_col_xcd"),
+    ({"NDFFT_COLSPLIT": "0"}, "ndfft", (4096, 24), 0, np.float64, "C", "transpose+pow2_reg"),
+    ({}, "nddct2", (4096, 64), 0, np.float64, "C", "transpose+pow2_real"),
+    ({"NDFFT_NARROW_DCT": "1"}, "nddct2", (4096, 64), 0, np.float64, "C", "pow2_col_xcd"),
+    ({}, "ndfft", (3000, 33), 0, np.float64, "C", "transpose+generic_row"),
+    ({}, "ndfft", (2, 32768), 1, np.float64, "C", "four_step"),
+    ({"NDFFT_FOURSTEP2": "0"}, "ndfft", (2, 32768), 1, np.float64, "C", "four_step"),
+    ({}, "ndfft", (3, 6000), 1, np.float64, "C", "four_step"),
+    ({}, "ndfft_r2c", (2, 65536), 1, np.float64, "C", "real_four_step"),
+    ({}, "ndifft_r2c", (2, 65536), 1, np.float64, "C", "real_four_step"),
+    ({}, "nddct3", (3, 131072), 1, np.float32, "C", "real_four_step"),
+    ({}, "nddct4", (2, 65536), 1, np.float64, "C", "real_four_step"),
+    ({}, "nddct1", (2, 65537), 1, np.float64, "C", "real_four_step"),
+    ({"NDFFT_REAL_FOURSTEP": "0"}, "ndfft_r2c", (2, 65536), 1, np.float64, "C", "four_step"),
+    ({"NDFFT_REAL_FOURSTEP": "0"}, "nddct4", (2, 65536), 1, np.float64, "C", "four_step"),
+    ({"NDFFT_REAL_FOURSTEP": "2"}, "nddct2", (2, 65536), 1, np.float64, "C", "real_four_step"),
+    ({}, "nddct2", (2, 12000), 1, np.float64, "C", "four_step"),
+    ({}, "nddct4", (2, 12000), 1, np.float64, "C", "four_step"),
+    ({}, "ndfft_r2c", (2, 9999), 1, np.float64, "C", "four_step"),
+    ({}, "ndfft", (20000, 3), 0, np.float64, "C", "transpose+four_step"),
+    ({}, "ndfft", (3, 4099), 1, np.float64, "C", "blue_global"),
+    ({}, "nddct2", (3, 4099), 1, np.float64, "C", "blue_global"),
+    ({}, "ndfft", (4099, 20), 0, np.float64, "C", "transpose+blue_global"),
+]
+# lanes of every second element on padded rows (neither rows nor adjacent lanes contiguous): (switches, op, n, dtype) -> last_path()
+ROUTE_TABLE_STEPPED = [
+    ({}, "ndfft", 7, np.float64, "tiny_strided"),
+    ({}, "nddct2", 12, np.float32, "tinymat_strided"),
+    ({"NDFFT_RADER": "0", "NDFFT_BLUE": "0"}, "ndfft", 97, np.float64, "generic_strided"),
+    ({}, "ndfft", 1 << 15, np.float64, "pack+four_step"),
+]
+
+
+def test_route_table(L):
+    """exec.hip's route choice, pinned: every route the emulation can reach (and the fallback kernels behind each route switch) on small cases of the
+    sizes above, results against the oracle."""
+    import synth
+    from helpers import TOL, assert_close, cdt_of
+    got = []
+    for env, name, shape, axis, rdt, layout, want in ROUTE_TABLE:
+        with ps.switches(L, **env):
+            got.append((name, shape, axis, ps.run_case(L, name, shape, axis, rdt, layout=layout), want))
+    for env, name, n, rdt, want in ROUTE_TABLE_STEPPED:
+        fn, ofn, _, in_c, out_c = ps.OPS[name]
+        with ps.switches(L, **env):
+            h, o = ps.handlers_for(name, n, rdt, L)
+            x = (synth.complex_array((3, 2 * n + 3), cdt_of(rdt)) if in_c else synth.real_array((3, 2 * n + 3), rdt))[:, 1:2 * n + 1:2]
+            y = np.zeros((3, n), cdt_of(rdt) if out_c else rdt); yo = np.zeros_like(y)
+            fn(x, y, h, 1)
+            got.append((name, (3, n), 1, L.last_path(), want))
+            ofn(np.ascontiguousarray(x), yo, o, 1)
+            assert_close(y, yo, 1, TOL[np.dtype(rdt)], f"{name} stepped n={n}")
+    bad = [g for g in got if g[3] != g[4]]
+    assert not bad, bad

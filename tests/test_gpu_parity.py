@@ -67,6 +67,27 @@ print("PATHS", p1, p2, p3)
     assert line[1:] == ["jit_col", "jit_col", "jit_reg"], f"prebuilt code objects missing or stale (paths {line[1:]}): run tools/prebuild_jit.py on an MI355X"
 
 
+def test_four_step_without_hiprtc_kernels_falls_back():
+    """Long lanes whose four-step factors are not powers of two run their two passes on hiprtc kernels.  When those cannot be had (here: NDFFT_JIT=cached
+    with no cache and no prebuilt objects) the pass declines and the call takes the route it took before round 6 -- the transpose form of the complex
+    four-step, the packed route of DCT-IV -- instead of failing (round-6 advisor, medium item)."""
+    import subprocess
+    import sys
+    code = r"""
+import sys, numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import parity_suite as ps
+from ndrustfft_amd import _lib
+L = _lib.default()
+print("PATHS", ps.run_case(L, "ndfft", (2, 196608), 1, np.float64), ps.run_case(L, "nddct4", (2, 163840), 1, np.float64))
+""" % (ROOT, os.path.join(ROOT, "tests"))
+    env = dict(os.environ, NDFFT_JIT="cached", NDFFT_JIT_CACHE="0", NDFFT_JIT_PREBUILT="0")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("PATHS")][-1].split()
+    assert line[1:] == ["four_step", "four_step"], line[1:]
+
+
 def test_regreal_tail_workgroup(L):
     """RegReal's tail workgroup clamps its staging addresses (predicated loads into AGPR-spilled registers once lost values on the
     MI355X, n = 40, 48 in f64): the product form on a partial last workgroup.  The predicated form is no longer in the product library
