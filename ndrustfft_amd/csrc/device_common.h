@@ -62,7 +62,7 @@ struct Pow2Args {
     // XCD-aware workgroup -> lane-block map (xcd_block): 0 = identity
     int32_t xcd_chunk = 0;
     // load policy of the input: -1 = the launcher decides by size, 0 = default policy (the input is expected in the Infinity Cache),
-    // 1 = streaming (nt) loads (the input comes from HBM) -- exec.hip: MallModel
+    // 1 = streaming (nt) loads (the input comes from HBM) -- exec_internal.h: MallModel
     int32_t stream_in = -1;
 };
 

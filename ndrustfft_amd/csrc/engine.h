@@ -183,6 +183,9 @@ const char *last_path();
 const std::string &last_err();
 void clear_err();
 int get_dev_tables(const ndfft_plan *plan, const DevTables **out);
+// host.hip: element range [lo, hi] (inclusive, relative to element 0) touched by a view -- also for shard.hip
+void view_range(int ndim, const int64_t *shape, const int64_t *stride, int64_t &lo, int64_t &hi, int64_t &count);
+
 // exec.hip: the argument checks of one nd* call (the reference's panics) without running it -- for shard.hip
 int validate_call(const ndfft_plan *plan, int op, int ndim, const int64_t *shape_in, const int64_t *stride_in, const int64_t *shape_out,
                   const int64_t *stride_out, int axis, int norm, double scale, bool *nothing);

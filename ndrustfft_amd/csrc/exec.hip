@@ -1,48 +1,22 @@
-// exec.hip -- ndfft_exec / ndfft_exec_device: the body of one nd* call.
+// exec.hip -- ndfft_exec_device and what every nd* call shares: the body of one call on device arrays.
 // Replaces the reference's lane iterator (create_transform! src/lib.rs:100-167 and its _par twin
 // 169-238): validation that mirrors the reference's panics, stride canonicalisation (the three
-// iterator strategies collapse into "every lane along `axis`, arbitrary signed strides"), kernel
-// choice, and -- for host arrays -- staging through HBM.
+// iterator strategies collapse into "every lane along `axis`, arbitrary signed strides") and kernel choice.  Host arrays are staged
+// through HBM by host.hip (ndfft_exec), which comes back here for prepare() and dispatch_peeled() (exec_internal.h).
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
-#include <deque>
 #include <mutex>
-#include <thread>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
 #include <type_traits>
-#if defined(__x86_64__) && !defined(NDFFT_NO_NT_COPY)
-#include <immintrin.h>   // host-side streaming copy of the bounce pipeline (bulk_copy)
-#endif
 
-#include "engine.h"
+#include "exec_internal.h"
 #include "pow2_real.h"
 
 namespace ndfft {
-
-struct BatchDim { int64_t shape, sin, sout; };
-
-struct Problem {
-    const ndfft_plan *plan;
-    int op;
-    int64_t xlen, ylen;          // lane lengths
-    int64_t xs, ys;              // axis strides
-    std::vector<BatchDim> b;     // merged batch dims, slowest first
-    int64_t nlanes;
-    double scale;
-    int keep_out = 0;            // column kernels: cache-allocating stores (the output is re-read right away, col_split)
-    int stream_in = 0;           // column kernels: streaming loads (the input must not evict a cache-resident intermediate)
-    int no_xcd_map = 0;          // column kernels: identity workgroup -> tile map (the stages of col_split: the map cost 7-20 us there)
-    int makhoul_out = 0;         // column C2R kernels: outputs through the inverse of Makhoul's permutation (last pass of real_fourstep_inv, DCT-III)
-};
-
-static size_t real_size(int dtype) { return dtype == NDFFT_F32 ? 4 : 8; }
-static bool op_in_cplx(int op) { return op == NDFFT_OP_C2C_FWD || op == NDFFT_OP_C2C_INV || op == NDFFT_OP_C2R; }
-static bool op_out_cplx(int op) { return op == NDFFT_OP_C2C_FWD || op == NDFFT_OP_C2C_INV || op == NDFFT_OP_R2C; }
 
 static int kind_of_op(int op) {
     if (op == NDFFT_OP_C2C_FWD || op == NDFFT_OP_C2C_INV) return NDFFT_KIND_C2C;
@@ -66,9 +40,9 @@ static int gen_op_of(int op, int n, int *slot) {
 }
 
 // validation shared by the host and device entry points; fills Problem. Returns 1 for "nothing to do".
-static int prepare(const ndfft_plan *plan, int op, int ndim, const int64_t *shape_in, const int64_t *stride_in,
-                   const int64_t *shape_out, const int64_t *stride_out, int axis, int norm, double scale,
-                   Problem &P, bool &nothing) {
+int prepare(const ndfft_plan *plan, int op, int ndim, const int64_t *shape_in, const int64_t *stride_in,
+            const int64_t *shape_out, const int64_t *stride_out, int axis, int norm, double scale,
+            Problem &P, bool &nothing) {
     nothing = false;
     if (!plan) return fail(NDFFT_ERR_INVALID_ARG, "plan is null");
     if (op < NDFFT_OP_C2C_FWD || op > NDFFT_OP_DCT4) return fail(NDFFT_ERR_INVALID_ARG, "bad op");
@@ -241,108 +215,8 @@ static int dispatch_generic(const Problem &P, const void *d_in, void *d_out, con
 }
 
 // ---------------------------------------------------------------------------------------------
-// Workspace of one host thread ON ONE DEVICE: scratch arrays of the multi-pass routes (keyed by stream; they
-// grow, never shrink), the staging buffers and pinned bounce buffers of ndfft_exec, and the streams / events of
-// its chunk pipeline.  A thread that alternates ndfft_set_device gets one of these per device (nothing allocated
-// on device 0 is ever handed to a kernel on device 1), and everything is released when the thread exits.
+// The workspaces of one host thread (exec_internal.h: DeviceWs), one per device it has used, released in one place
 // ---------------------------------------------------------------------------------------------
-struct Scratch { void *p = nullptr; size_t cap = 0; };
-struct Staging {
-    void *p = nullptr; size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return NDFFT_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        NDFFT_HIP(hipMalloc(&p, bytes));
-        cap = bytes;
-        return NDFFT_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-struct PinnedBuf {
-    void *p = nullptr; size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return NDFFT_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        NDFFT_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-        cap = bytes;
-        return NDFFT_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
-struct Pipe {
-    hipStream_t h2d = nullptr, cmp = nullptr, d2h = nullptr;
-    std::vector<hipEvent_t> up, done, down;
-    bool ok = false;
-    void sync_all() { if (ok) { (void)hipStreamSynchronize(h2d); (void)hipStreamSynchronize(cmp); (void)hipStreamSynchronize(d2h); } }
-    void release() {
-        if (!ok) return;
-        sync_all();
-        for (auto *v : {&up, &done, &down}) { for (hipEvent_t e : *v) (void)hipEventDestroy(e); v->clear(); }
-        (void)hipStreamDestroy(h2d); (void)hipStreamDestroy(cmp); (void)hipStreamDestroy(d2h);
-        h2d = cmp = d2h = nullptr; ok = false;
-    }
-};
-// What this thread's own calls imply about the 256 MiB Infinity Cache of the current device -- used for ONE decision, the load
-// policy of the row / column-tile kernels that have a streaming-load form (BASELINE configs[1], [3], [4]): plain loads are up to 15 %
-// faster when the input is resident in the Infinity Cache (4096 x 4096 c128: 0.86 vs 0.74 of the roofline), streaming (nt) loads 6 %
-// faster when it comes from HBM (0.74 vs 0.70).  Round 2 bet on "resident" for every input <= 384 MiB; a chain of nd* calls loses that bet
-// at every link (the output of a pass was written with nt stores, which bypass the cache).  The model is an LRU stack distance per buffer
-// this thread has transformed:
-//   * a buffer this thread WROTE as an output of more than 64 MiB is cold (nt stores) -> streaming loads when it becomes an input;
-//   * a buffer it READ before (with either policy), or wrote as a small output, is worth plain loads iff the bytes this thread has moved
-//     through the cache since (all inputs, small outputs) plus its own size fit ~256 MiB: a re-read input then is, or becomes, resident;
-//     six rotating 256 MiB inputs never are (streaming loads for all of them);
-//   * a buffer the model has never seen keeps round 2's size rule (plain loads up to 384 MiB) -- its producer is unknown.
-// A stale entry (the allocator reused the addresses for something a foreign kernel produced) costs one call: after that the buffer is "read".
-// ndfft_set_input_hint overrides the model per host thread.  Speed only: either policy gives the same results.
-struct MallModel {
-    enum State { READ = 0, OUT_SMALL = 1, OUT_COLD = 2 };
-    struct Entry { uintptr_t lo, hi; uint64_t stamp; int state; };
-    std::vector<Entry> e;
-    uint64_t clock = 0;                          // bytes this thread has moved through the cache's address stream (inputs read, small outputs)
-    static constexpr uint64_t kCap = (uint64_t)256 << 20, kSmallOut = (uint64_t)64 << 20;
-    Entry *find(const void *p, size_t bytes) {
-        const uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
-        for (auto &x : e) if (lo < x.hi && x.lo < hi) return &x;
-        return nullptr;
-    }
-    // 1: streaming loads, 0: plain loads, -1: unknown buffer (the launcher decides by size)
-    int decide(const void *in, size_t bytes) {
-        const Entry *x = find(in, bytes);
-        if (!x) return -1;
-        if (x->state == OUT_COLD) return 1;
-        // a buffer larger than the cache (BASELINE configs[2]'s 4097 x 8192 c64 is 64 KiB over): only an IMMEDIATE re-read still finds most of it
-        // there (the size rule decides, as for an unknown buffer); anything else this thread has read since has pushed it out -- round 5: the
-        // rotating-pairs table ran this shape with plain loads (policy 0), 95.9 us against 92 us with streaming loads
-        if (bytes > kCap) return clock == x->stamp ? -1 : 1;
-        return clock - x->stamp + bytes <= kCap ? 0 : 1;
-    }
-    void put(const void *p, size_t bytes, int state, bool through_cache) {
-        const uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
-        for (size_t i = 0; i < e.size();) { if (lo < e[i].hi && e[i].lo < hi) e.erase(e.begin() + i); else ++i; }
-        if (through_cache) clock += bytes;
-        if (e.size() >= 32) e.erase(e.begin());  // oldest first
-        e.push_back({lo, hi, clock, state});
-    }
-    void note_read(const void *p, size_t bytes) { put(p, bytes, READ, true); }
-    void note_write(const void *p, size_t bytes) { if (bytes <= kSmallOut) put(p, bytes, OUT_SMALL, true); else put(p, bytes, OUT_COLD, false); }
-};
-struct DeviceWs {
-    MallModel mall;
-    std::map<hipStream_t, Scratch> scratch[8];
-    Staging stage_in, stage_out;
-    PinnedBuf bounce_in[3], bounce_out[3];
-    Pipe pipe;
-    void release() {   // the owning device must be current
-        pipe.release();
-        for (auto &m : scratch) { for (auto &kv : m) if (kv.second.p) (void)hipFree(kv.second.p); m.clear(); }
-        stage_in.release(); stage_out.release();
-        for (auto &b : bounce_in) b.release();
-        for (auto &b : bounce_out) b.release();
-    }
-};
 struct ThreadWs {
     std::map<int, DeviceWs> dev;
     void release_all() {
@@ -356,7 +230,7 @@ struct ThreadWs {
     ~ThreadWs() { release_all(); }   // a worker thread that exits gives its device memory and streams back
 };
 static thread_local ThreadWs g_tws;
-static int current_ws(DeviceWs **out) {
+int current_ws(DeviceWs **out) {
     int dev = 0;
     NDFFT_HIP(hipGetDevice(&dev));
     *out = &g_tws.dev[dev];
@@ -365,7 +239,7 @@ static int current_ws(DeviceWs **out) {
 static thread_local int g_input_hint = NDFFT_INPUT_AUTO;
 static thread_local int g_last_policy = -1;       // load policy the last call on this thread asked the model for (diagnostic)
 static bool F_nt_ok(int F) { return F >= 64; }   // (short lanes: the staging loads are not 16-byte vectors on every path)
-// load policy for the dense C2C row kernels on input `in` (Pow2Args::stream_in), and the bookkeeping for the next call
+// load policy for the dense C2C row kernels on input `in` (Pow2Args::stream_in), and the bookkeeping for the next call (the model: exec_internal.h, MallModel)
 static int row_load_policy(const void *in, size_t bytes, const void *out, size_t out_bytes);
 static int c2c_row_load_policy(const void *in, const void *out, size_t bytes) { return row_load_policy(in, bytes, out, bytes); }
 static int row_load_policy(const void *in, size_t bytes, const void *out, size_t out_bytes) {
@@ -397,9 +271,7 @@ static int get_scratch(int which, hipStream_t s, size_t bytes, void **out) {
 
 static int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t stream);
 
-// A route of dispatch() returns NDFFT_OK, a real error (returned to the caller), or kDeclined: "not mine, the next route runs".
-// kDeclined is no ndfft status and never leaves dispatch().
-constexpr int kDeclined = -1;
+// (the result of a route: exec_internal.h, kDeclined)
 // A hiprtc launcher's NDFFT_ERR_UNSUPPORTED (no hiprtc, a failed compile or module load, NDFFT_JIT=cached with nothing cached) declines its route.
 static int jit_rc(int rc) { return rc == NDFFT_ERR_UNSUPPORTED ? kDeclined : rc; }
 // a route's result: its path is recorded unless it declined
@@ -1247,7 +1119,7 @@ static int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t
 }
 
 // more than kMaxBatchDims un-mergeable batch dims: peel the slowest ones on the host
-static int dispatch_peeled(Problem &P, const char *d_in, char *d_out, size_t ein, size_t eout, hipStream_t stream) {
+int dispatch_peeled(Problem &P, const char *d_in, char *d_out, size_t ein, size_t eout, hipStream_t stream) {
     if (P.b.size() <= (size_t)kMaxBatchDims) return dispatch(P, d_in, d_out, stream);
     BatchDim outer = P.b.front();
     Problem Q = P;
@@ -1260,391 +1132,9 @@ static int dispatch_peeled(Problem &P, const char *d_in, char *d_out, size_t ein
     return NDFFT_OK;
 }
 
-// element range [lo, hi] (inclusive, relative to element 0) touched by a view
-static void view_range(int ndim, const int64_t *shape, const int64_t *stride, int64_t &lo, int64_t &hi, int64_t &count) {
-    lo = hi = 0; count = 1;
-    for (int d = 0; d < ndim; ++d) {
-        count *= shape[d];
-        if (shape[d] <= 0) continue;
-        const int64_t ext = (shape[d] - 1) * stride[d];
-        if (ext < 0) lo += ext; else hi += ext;
-    }
-}
-
-// Copies exactly the elements of an n-d view between two byte images of the same address range (`dst` and `src`
-// both point at the image of element 0).  Used for output views with holes: the device result comes back as an
-// image of the view's whole span, and only the elements the view OWNS may be written to the caller's memory --
-// Rust's `&mut ArrayViewMut` guarantees exclusivity of those elements only (two threads may hold interleaved
-// views of one allocation, e.g. even / odd columns from multi_slice_mut).
-static void copy_view_elements(char *dst, const char *src, int ndim, const int64_t *shape, const int64_t *stride, size_t esz) {
-    struct D { int64_t n, s; };
-    std::vector<D> d;
-    for (int k = 0; k < ndim; ++k) {
-        if (shape[k] == 0) return;
-        if (shape[k] > 1 && stride[k] != 0) d.push_back({shape[k], stride[k]});
-    }
-    std::sort(d.begin(), d.end(), [](const D &a, const D &b) { return std::llabs(a.s) < std::llabs(b.s); });
-    // innermost contiguous run (|stride| == 1), merged with outer dims that continue it
-    int64_t run = 1, run_off = 0;   // run_off: offset of the run's lowest element relative to the index-0 element
-    size_t first = 0;
-    if (!d.empty() && std::llabs(d[0].s) == 1) {
-        run = d[0].n; run_off = d[0].s < 0 ? -(d[0].n - 1) : 0; first = 1;
-        while (first < d.size() && d[first].s == run && run_off == 0) { run *= d[first].n; ++first; }
-    }
-    std::vector<D> o(d.begin() + first, d.end());
-    std::vector<int64_t> idx(o.size(), 0);
-    int64_t off = 0;
-    for (;;) {
-        memcpy(dst + (off + run_off) * (int64_t)esz, src + (off + run_off) * (int64_t)esz, (size_t)run * esz);
-        size_t k = 0;
-        for (; k < o.size(); ++k) {
-            off += o[k].s;
-            if (++idx[k] < o[k].n) break;
-            off -= o[k].s * o[k].n; idx[k] = 0;
-        }
-        if (k == o.size()) break;
-    }
-}
-
 }  // namespace ndfft
 
 using namespace ndfft;
-
-namespace {
-// ---- pinned host arrays: H2D || kernel || D2H over row chunks --------------------------------------------
-// Pageable host memory is staged by the runtime and the two PCIe directions do not overlap (tools/h2d_bench.hip:
-// 9.7 ms for 2 x 256 MiB whatever the threading); arrays allocated with ndfft_host_alloc are pinned, their copies
-// are real DMA and the directions overlap (5.6 ms).  A dense C-layout call whose slowest dimension is a batch
-// dimension is therefore split into row chunks: chunk c+1 uploads while chunk c transforms and chunk c-1 downloads.
-bool is_pinned(const void *p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-
-// ---- registration cache for the caller's own (pageable) arrays ---------------------------------------------------------
-// The reference's signature hands over ndarrays in ordinary host memory (src/lib.rs:105-115).  Pinned memory moves at the PCIe duplex
-// rate (2 x 256 MiB: 6.2 ms through the chunk pipeline) but hipHostRegister costs ~22 ms per 512 MiB, pageable memory goes through bounce
-// buffers (8-10 ms: the host memcpys bound it on a 16-CPU quota).  A caller that transforms the SAME arrays again and again -- a time
-// stepper, the reference's own benches -- should pay the registration once: the SECOND time a range is seen it is registered and kept in an
-// LRU, from then on its calls run the pinned pipeline.  One-shot arrays never pay.
-// OPT-IN (ndfft_host_reg_cache / NDFFT_HOST_REG_CACHE_MB, default 0 = off), because a registration outlives the array: when the caller
-// frees a registered array and the allocator hands the addresses out again, HIP still treats them as the old pinned object and EVERY copy
-// from or to them -- this library's, torch's, the caller's own -- fails with "invalid argument" or aborts inside the HIP runtime (both seen
-// on the MI355X with numpy arrays in the first version, which had the cache on by default).  This library recovers from the error form
-// (it forgets the range and retries through the bounce buffers) but cannot protect other code nor survive the abort, so only a caller that
-// owns its arrays' lifetimes should switch it on, and it must call ndfft_host_forget before freeing them.
-class HostRegCache {
-  public:
-    static HostRegCache &get() { static HostRegCache *c = new HostRegCache; return *c; }
-    // true: [p, p + bytes) lies inside a registration THIS CACHE owns, and is held until release(): its LRU stamp is fresh and neither
-    // eviction, forget() nor set_limit(0) will unregister it while the call's copies are in flight.  Asked BEFORE is_pinned() (round 4: a
-    // registered array looks like any pinned one to hipPointerGetAttributes, and the steady-state calls used to bypass the cache -- the
-    // hottest arrays were evicted first, nothing held them during the DMA, and a stale registration was not retried).
-    // Two steps (round 5, advisor): lookup() only consults the registrations this cache owns; sight() records a sighting of a range and registers it
-    // on the second one.  HostPin calls sight() only for memory that is NOT pinned already: an ndfft_host_alloc / hipHostMalloc array that missed the
-    // lookup is the caller's own pinned memory -- registering it again would either fail every time or leave the cache owning (and later
-    // unregistering) a registration over memory the caller frees with hipHostFree.
-    bool lookup(const void *p, size_t bytes) {
-        const uintptr_t lo = (uintptr_t)p, hi = lo + std::max<size_t>(bytes, 1);
-        std::lock_guard<std::mutex> g(mu_);
-        ++tick_;
-        for (R &r : v_) if (r.registered && r.lo <= lo && hi <= r.hi) { r.last = tick_; ++r.inuse; return true; }   // any size: sub-views of a registered array too
-        return false;
-    }
-    bool wants(size_t bytes) { std::lock_guard<std::mutex> g(mu_); return limit_ && bytes >= ((size_t)8 << 20); }
-    bool sight(const void *p, size_t bytes) {
-        const uintptr_t lo = (uintptr_t)p, hi = lo + std::max<size_t>(bytes, 1);
-        std::lock_guard<std::mutex> g(mu_);
-        ++tick_;
-        if (!limit_ || bytes < ((size_t)8 << 20)) return false;
-        for (size_t i = 0; i < v_.size();) {
-            R &r = v_[i];
-            if (!(r.lo == lo && r.hi == hi) && lo < r.hi && r.lo < hi) {   // overlaps another range: the caller's allocation changed (an unregistered sighting
-                if (r.inuse) return false;                                //   of a larger, older array must not be what gets pinned -- only the range of THIS call is)
-                drop(i);
-                continue;
-            }
-            ++i;
-        }
-        R *hit = nullptr;                                 // (looked up after the erasures above: they move entries)
-        for (R &r : v_) if (r.lo == lo && r.hi == hi) { hit = &r; break; }
-        if (hit) {
-            hit->last = tick_;
-            if (++hit->seen < 2) return false;            // (after a failed registration `seen` restarts at -8: a bounded back-off, not a ban)
-            if (hipHostRegister((void *)lo, hi - lo, hipHostRegisterDefault) != hipSuccess) { (void)hipGetLastError(); hit->seen = -8; return false; }
-            hit->registered = true; hit->inuse = 1; reg_bytes_ += hi - lo;
-            evict(lo);                                    // (evict() may move entries: `hit` is dead from here)
-            return true;
-        }
-        if (v_.size() >= 256) {                           // forget the oldest unregistered sighting
-            size_t o = v_.size();
-            for (size_t i = 0; i < v_.size(); ++i) if (!v_[i].registered && (o == v_.size() || v_[i].last < v_[o].last)) o = i;
-            if (o < v_.size()) v_.erase(v_.begin() + o);
-        }
-        v_.push_back({lo, hi, tick_, 1, false, 0});
-        return false;
-    }
-    void release(const void *p) {
-        const uintptr_t a = (uintptr_t)p;
-        std::lock_guard<std::mutex> g(mu_);
-        for (R &r : v_) if (r.registered && r.lo <= a && a < r.hi && r.inuse > 0) { --r.inuse; return; }
-    }
-    // p == nullptr: everything.  Returns the number of registrations given back.
-    int forget(const void *p) {
-        const uintptr_t a = (uintptr_t)p;
-        std::lock_guard<std::mutex> g(mu_);
-        int n = 0;
-        for (size_t i = 0; i < v_.size();) {
-            if ((!p || (v_[i].lo <= a && a < v_[i].hi)) && !v_[i].inuse) { n += v_[i].registered; drop(i); } else ++i;
-        }
-        return n;
-    }
-  private:
-    struct R { uintptr_t lo, hi; uint64_t last; int seen; bool registered; int inuse; };
-    HostRegCache() { limit_ = (size_t)std::max(0L, sw().host_reg_cache_mb) << 20; }
-  public:
-    void set_limit(size_t bytes) {
-        std::lock_guard<std::mutex> g(mu_);
-        limit_ = bytes;
-        if (!bytes) { for (size_t i = 0; i < v_.size();) { if (!v_[i].inuse) drop(i); else ++i; } }
-        else evict(0);
-    }
-  private:
-    void drop(size_t i) {
-        if (v_[i].registered) { (void)hipHostUnregister((void *)v_[i].lo); (void)hipGetLastError(); reg_bytes_ -= v_[i].hi - v_[i].lo; }
-        v_.erase(v_.begin() + i);
-    }
-    void evict(uintptr_t keep) {
-        while (reg_bytes_ > limit_) {
-            size_t o = v_.size();
-            for (size_t i = 0; i < v_.size(); ++i)
-                if (v_[i].registered && !v_[i].inuse && v_[i].lo != keep && (o == v_.size() || v_[i].last < v_[o].last)) o = i;
-            if (o == v_.size()) return;
-            drop(o);
-        }
-    }
-    std::mutex mu_;
-    std::vector<R> v_;
-    uint64_t tick_ = 0;
-    size_t reg_bytes_ = 0, limit_ = 0;
-};
-struct HostPin {       // one side of a call: registered for the duration of the call if the cache says so
-    const void *p = nullptr; bool held = false;
-    HostPin(const void *ptr, size_t bytes) : p(ptr) {
-        HostRegCache &c = HostRegCache::get();
-        held = c.lookup(ptr, bytes);
-        if (!held && c.wants(bytes) && !is_pinned(ptr)) held = c.sight(ptr, bytes);
-    }
-    ~HostPin() { if (held) HostRegCache::get().release(p); }
-};
-int pipe_init(Pipe &p, int chunks) {
-    if (!p.ok) {
-        NDFFT_HIP(hipStreamCreate(&p.h2d)); NDFFT_HIP(hipStreamCreate(&p.cmp)); NDFFT_HIP(hipStreamCreate(&p.d2h));
-        p.ok = true;
-    }
-    while ((int)p.up.size() < chunks) {
-        hipEvent_t a, b, c;
-        NDFFT_HIP(hipEventCreateWithFlags(&a, hipEventDisableTiming)); NDFFT_HIP(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-        NDFFT_HIP(hipEventCreateWithFlags(&c, hipEventDisableTiming));
-        p.up.push_back(a); p.done.push_back(b); p.down.push_back(c);
-    }
-    return NDFFT_OK;
-}
-// span (in elements) of one index of dimension 0, i.e. of the sub-view shape[1:], or -1 if it has negative strides
-int64_t inner_span(int ndim, const int64_t *shape, const int64_t *stride) {
-    int64_t hi = 0;
-    for (int d = 1; d < ndim; ++d) {
-        if (shape[d] <= 0) return 0;
-        if (stride[d] < 0) return -1;
-        hi += (shape[d] - 1) * stride[d];
-    }
-    return hi + 1;
-}
-}  // namespace
-
-static int exec_pinned_pipeline_body(DeviceWs &ws, const ndfft_plan *plan, int op, const char *hin, char *hout, int ndim, const int64_t *shape_in,
-                                     const int64_t *stride_in, const int64_t *shape_out, const int64_t *stride_out, int axis, int norm,
-                                     double scale, size_t ein, size_t eout, int chunks) {
-    int rc;
-    Pipe &pp = ws.pipe;
-    if ((rc = pipe_init(pp, chunks))) return rc;
-    const int64_t R = shape_in[0];
-    const int64_t isp = inner_span(ndim, shape_in, stride_in), osp = inner_span(ndim, shape_out, stride_out);
-    std::vector<int64_t> si(shape_in, shape_in + ndim), so(shape_out, shape_out + ndim);
-    for (int c = 0; c < chunks; ++c) {
-        const int64_t r0 = R * c / chunks, r1 = R * (c + 1) / chunks;
-        if (r1 <= r0) continue;
-        si[0] = so[0] = r1 - r0;
-        const size_t off_in = (size_t)(r0 * stride_in[0]) * ein, off_out = (size_t)(r0 * stride_out[0]) * eout;
-        const size_t bytes_in = (size_t)((r1 - r0 - 1) * stride_in[0] + isp) * ein, bytes_out = (size_t)((r1 - r0 - 1) * stride_out[0] + osp) * eout;
-        NDFFT_HIP(hipMemcpyAsync((char *)ws.stage_in.p + off_in, hin + off_in, bytes_in, hipMemcpyHostToDevice, pp.h2d));
-        NDFFT_HIP(hipEventRecord(pp.up[c], pp.h2d));
-        NDFFT_HIP(hipStreamWaitEvent(pp.cmp, pp.up[c], 0));
-        Problem P;
-        bool nothing;
-        if ((rc = prepare(plan, op, ndim, si.data(), stride_in, so.data(), stride_out, axis, norm, scale, P, nothing))) return rc;
-        if (!nothing && (rc = dispatch_peeled(P, (const char *)ws.stage_in.p + off_in, (char *)ws.stage_out.p + off_out, ein, eout, pp.cmp))) return rc;
-        NDFFT_HIP(hipEventRecord(pp.done[c], pp.cmp));
-        NDFFT_HIP(hipStreamWaitEvent(pp.d2h, pp.done[c], 0));
-        NDFFT_HIP(hipMemcpyAsync(hout + off_out, (const char *)ws.stage_out.p + off_out, bytes_out, hipMemcpyDeviceToHost, pp.d2h));
-    }
-    NDFFT_HIP(hipStreamSynchronize(pp.d2h));
-    NDFFT_HIP(hipStreamSynchronize(pp.cmp));
-    return NDFFT_OK;
-}
-static int exec_pinned_pipeline(DeviceWs &ws, const ndfft_plan *plan, int op, const char *hin, char *hout, int ndim, const int64_t *shape_in,
-                                const int64_t *stride_in, const int64_t *shape_out, const int64_t *stride_out, int axis, int norm,
-                                double scale, size_t ein, size_t eout, int chunks) {
-    const int rc = exec_pinned_pipeline_body(ws, plan, op, hin, hout, ndim, shape_in, stride_in, shape_out, stride_out, axis, norm, scale, ein, eout, chunks);
-    // on an error some chunks' asynchronous copies into the caller's arrays (and into the staging buffers, which the
-    // next call may regrow) are still in flight: never return before they have drained
-    if (rc) ws.pipe.sync_all();
-    return rc;
-}
-
-// ---- pageable host arrays: the same chunk pipeline through pinned bounce buffers --------------------------------
-// hipMemcpy from / to pageable memory is staged by the runtime on one thread, and the two PCIe directions never overlap
-// (tools/h2d_bench.hip: 9.7 ms for 2 x 256 MiB).  Here the staging is ours: a small pool of host threads copies row
-// chunks between the caller's arrays and three pinned slots per direction while the DMA engines move the previous
-// chunks, so upload, transform and download overlap for ANY host array (ndarray allocates pageable memory).
-namespace {
-// Bulk host copy with streaming (non-temporal) stores: the pieces the pool moves (a few MiB each) are below glibc's own non-temporal threshold, so plain
-// memcpy reads the destination lines before overwriting them (three memory transfers per byte instead of two).  AVX2 only where the CPU has it;
-// (-DNDFFT_NO_NT_COPY keeps memcpy).  Host code only.
-#if defined(__x86_64__) && !defined(NDFFT_NO_NT_COPY)
-__attribute__((target("avx2"))) void copy_nt_avx2(char *d, const char *s, size_t n) {
-    while (n && ((uintptr_t)d & 31)) { *d++ = *s++; --n; }
-    size_t k = n / 128;
-    for (; k; --k, d += 128, s += 128) {
-        const __m256i a = _mm256_loadu_si256((const __m256i *)s), b = _mm256_loadu_si256((const __m256i *)(s + 32));
-        const __m256i c = _mm256_loadu_si256((const __m256i *)(s + 64)), e = _mm256_loadu_si256((const __m256i *)(s + 96));
-        _mm256_stream_si256((__m256i *)d, a); _mm256_stream_si256((__m256i *)(d + 32), b);
-        _mm256_stream_si256((__m256i *)(d + 64), c); _mm256_stream_si256((__m256i *)(d + 96), e);
-    }
-    _mm_sfence();
-    n &= 127;
-    if (n) memcpy(d, s, n);
-}
-void bulk_copy(char *d, const char *s, size_t n) {
-    static const bool nt = __builtin_cpu_supports("avx2");
-    if (nt && n >= ((size_t)256 << 10)) copy_nt_avx2(d, s, n); else memcpy(d, s, n);
-}
-#else
-void bulk_copy(char *d, const char *s, size_t n) { memcpy(d, s, n); }
-#endif
-struct CopyGroup { std::atomic<int> left{0}; std::mutex m; std::condition_variable cv; };
-class CopyPool {
-  public:
-    static CopyPool &get() { static CopyPool *p = new CopyPool; return *p; }   // never destroyed: detached workers
-    int threads() const { return nthreads_; }
-    // copies `bytes` in `pieces` slices on the pool; returns immediately
-    void copy_async(CopyGroup &g, char *dst, const char *src, size_t bytes, int pieces) {
-        pieces = (int)std::max<size_t>(1, std::min<size_t>((size_t)pieces, bytes / (256 << 10) + 1));
-        g.left.store(pieces);
-        const size_t per = (bytes / pieces + 63) & ~(size_t)63;
-        std::lock_guard<std::mutex> lk(mu_);
-        for (int i = 0; i < pieces; ++i) {
-            const size_t o = std::min(bytes, (size_t)i * per), e = i + 1 == pieces ? bytes : std::min(bytes, (size_t)(i + 1) * per);
-            q_.push_back({dst + o, src + o, e - o, &g});
-        }
-        cv_.notify_all();
-    }
-    static void wait(CopyGroup &g) {
-        std::unique_lock<std::mutex> lk(g.m);
-        g.cv.wait(lk, [&] { return g.left.load() == 0; });
-    }
-  private:
-    struct Piece { char *d; const char *s; size_t n; CopyGroup *g; };
-    CopyPool() {
-        // threads: three quarters of the CPUs this process may use (affinity / hardware count capped by the cgroup quota:
-        // the MI355X boxes show 256 CPUs and grant 16), between 2 and 12.  Measured on 4096 x 4096 c128 (2 x 256 MiB,
-        // plain path 9.8 ms): 4 threads 9.5-10.6 ms, 8 threads 8.8 ms, 12 threads 7.9-8.4 ms -- the host copies, not PCIe, bound it
-        const int forced = sw().copy_threads;            // NDFFT_COPY_THREADS
-        long hw = (long)std::thread::hardware_concurrency();
-        if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-            char q[32] = {0}; long per = 0;
-            if (fscanf(f, "%31s %ld", q, &per) == 2 && strcmp(q, "max") != 0 && per > 0) hw = std::min(hw, std::max(1L, (atol(q) + per - 1) / per));
-            fclose(f);
-        }
-        nthreads_ = forced > 0 ? forced : (int)std::max(2L, std::min(12L, hw * 3 / 4));
-        if (nthreads_ < 1) nthreads_ = 1;
-        for (int i = 0; i < nthreads_; ++i) std::thread([this] { loop(); }).detach();
-    }
-    void loop() {
-        for (;;) {
-            Piece p;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [this] { return !q_.empty(); });
-                p = q_.front(); q_.pop_front();
-            }
-            bulk_copy(p.d, p.s, p.n);
-            // the count changes only under the group's mutex: a waiter (whose CopyGroup lives on its stack) cannot see zero, return and
-            // destroy the group while this thread is still about to lock it
-            { std::lock_guard<std::mutex> lk(p.g->m); if (p.g->left.fetch_sub(1) == 1) p.g->cv.notify_all(); }
-        }
-    }
-    int nthreads_ = 1;
-    std::mutex mu_;
-    std::condition_variable cv_;
-    std::deque<Piece> q_;
-};
-}  // namespace
-
-static int exec_bounce_pipeline_body(DeviceWs &ws, const ndfft_plan *plan, int op, const char *hin, char *hout, int ndim, const int64_t *shape_in,
-                                     const int64_t *stride_in, const int64_t *shape_out, const int64_t *stride_out, int axis, int norm,
-                                     double scale, size_t ein, size_t eout, int chunks) {
-    int rc;
-    Pipe &pp = ws.pipe;
-    if ((rc = pipe_init(pp, chunks))) return rc;
-    CopyPool &pool = CopyPool::get();
-    const int64_t R = shape_in[0];
-    const int64_t isp = inner_span(ndim, shape_in, stride_in), osp = inner_span(ndim, shape_out, stride_out);
-    auto r0_of = [&](int c) { return R * c / chunks; };
-    auto off_in = [&](int c) { return (size_t)(r0_of(c) * stride_in[0]) * ein; };
-    auto off_out = [&](int c) { return (size_t)(r0_of(c) * stride_out[0]) * eout; };
-    auto bytes_in = [&](int c) { const int64_t n = r0_of(c + 1) - r0_of(c); return n <= 0 ? (size_t)0 : (size_t)((n - 1) * stride_in[0] + isp) * ein; };
-    auto bytes_out = [&](int c) { const int64_t n = r0_of(c + 1) - r0_of(c); return n <= 0 ? (size_t)0 : (size_t)((n - 1) * stride_out[0] + osp) * eout; };
-    size_t max_in = 0, max_out = 0;
-    for (int c = 0; c < chunks; ++c) { max_in = std::max(max_in, bytes_in(c)); max_out = std::max(max_out, bytes_out(c)); }
-    for (int k = 0; k < 3; ++k) { if ((rc = ws.bounce_in[k].reserve(max_in)) || (rc = ws.bounce_out[k].reserve(max_out))) return rc; }
-    std::vector<int64_t> si(shape_in, shape_in + ndim), so(shape_out, shape_out + ndim);
-    const int half = std::max(1, pool.threads() / 2);
-    CopyGroup gu, gd;
-    for (int it = 0; it < chunks + 2; ++it) {
-        const int cu = it, cd = it - 2;
-        const bool up = cu < chunks && bytes_in(cu) > 0, dn = cd >= 0 && bytes_out(cd) > 0;
-        // (both waits BEFORE any pool copy is submitted: an error return must never leave the pool working on gu / gd)
-        if (up && cu >= 3) NDFFT_HIP(hipEventSynchronize(pp.up[cu - 3]));      // the slot's previous upload has left it
-        if (dn) NDFFT_HIP(hipEventSynchronize(pp.down[cd]));                    // chunk cd has arrived in its slot
-        if (up) pool.copy_async(gu, (char *)ws.bounce_in[cu % 3].p, hin + off_in(cu), bytes_in(cu), half);
-        if (dn) pool.copy_async(gd, hout + off_out(cd), (const char *)ws.bounce_out[cd % 3].p, bytes_out(cd), half);
-        if (up) CopyPool::wait(gu);
-        if (dn) CopyPool::wait(gd);
-        if (!up) continue;
-        NDFFT_HIP(hipMemcpyAsync((char *)ws.stage_in.p + off_in(cu), ws.bounce_in[cu % 3].p, bytes_in(cu), hipMemcpyHostToDevice, pp.h2d));
-        NDFFT_HIP(hipEventRecord(pp.up[cu], pp.h2d));
-        NDFFT_HIP(hipStreamWaitEvent(pp.cmp, pp.up[cu], 0));
-        si[0] = so[0] = r0_of(cu + 1) - r0_of(cu);
-        Problem P;
-        bool nothing;
-        if ((rc = prepare(plan, op, ndim, si.data(), stride_in, so.data(), stride_out, axis, norm, scale, P, nothing))) return rc;
-        if (!nothing && (rc = dispatch_peeled(P, (const char *)ws.stage_in.p + off_in(cu), (char *)ws.stage_out.p + off_out(cu), ein, eout, pp.cmp))) return rc;
-        NDFFT_HIP(hipEventRecord(pp.done[cu], pp.cmp));
-        NDFFT_HIP(hipStreamWaitEvent(pp.d2h, pp.done[cu], 0));
-        NDFFT_HIP(hipMemcpyAsync(ws.bounce_out[cu % 3].p, (const char *)ws.stage_out.p + off_out(cu), bytes_out(cu), hipMemcpyDeviceToHost, pp.d2h));
-        NDFFT_HIP(hipEventRecord(pp.down[cu], pp.d2h));
-    }
-    return NDFFT_OK;
-}
-static int exec_bounce_pipeline(DeviceWs &ws, const ndfft_plan *plan, int op, const char *hin, char *hout, int ndim, const int64_t *shape_in,
-                                const int64_t *stride_in, const int64_t *shape_out, const int64_t *stride_out, int axis, int norm,
-                                double scale, size_t ein, size_t eout, int chunks) {
-    const int rc = exec_bounce_pipeline_body(ws, plan, op, hin, hout, ndim, shape_in, stride_in, shape_out, stride_out, axis, norm, scale, ein, eout, chunks);
-    if (rc) ws.pipe.sync_all();   // (pool copies are always waited for inside the body; only device work can be in flight)
-    return rc;
-}
 
 extern "C" {
 
@@ -1661,136 +1151,6 @@ int ndfft_exec_device(const ndfft_plan *plan, int op, const void *d_in, void *d_
     const size_t r = real_size(plan->dtype);
     return dispatch_peeled(P, (const char *)d_in, (char *)d_out, op_in_cplx(op) ? 2 * r : r, op_out_cplx(op) ? 2 * r : r,
                            (hipStream_t)stream);
-}
-
-int ndfft_host_alloc(void **h_ptr, size_t bytes) {
-    clear_err();
-    if (!h_ptr) return fail(NDFFT_ERR_INVALID_ARG, "h_ptr is null");
-    NDFFT_HIP(hipHostMalloc(h_ptr, bytes ? bytes : 1, hipHostMallocDefault));
-    return NDFFT_OK;
-}
-int ndfft_host_free(void *h_ptr) {
-    clear_err();
-    if (h_ptr) NDFFT_HIP(hipHostFree(h_ptr));
-    return NDFFT_OK;
-}
-
-int ndfft_exec(const ndfft_plan *plan, int op, const void *in, void *out, int ndim, const int64_t *shape_in,
-               const int64_t *stride_in, const int64_t *shape_out, const int64_t *stride_out, int axis, int norm,
-               double scale) {
-    clear_err();
-    Problem P;
-    bool nothing;
-    int rc = prepare(plan, op, ndim, shape_in, stride_in, shape_out, stride_out, axis, norm, scale, P, nothing);
-    if (rc || nothing) return rc;
-    if (!in || !out) return fail(NDFFT_ERR_INVALID_ARG, "null array pointer");
-    DeviceWs *wsp;
-    if ((rc = current_ws(&wsp))) return rc;
-    DeviceWs &ws = *wsp;
-    const size_t r = real_size(plan->dtype);
-    const size_t ein = op_in_cplx(op) ? 2 * r : r, eout = op_out_cplx(op) ? 2 * r : r;
-    int64_t ilo, ihi, icnt, olo, ohi, ocnt;
-    view_range(ndim, shape_in, stride_in, ilo, ihi, icnt);
-    view_range(ndim, shape_out, stride_out, olo, ohi, ocnt);
-    const size_t ibytes = (size_t)(ihi - ilo + 1) * ein, obytes = (size_t)(ohi - olo + 1) * eout;
-    const char *hin = (const char *)in + ilo * (int64_t)ein;
-    char *hout = (char *)out + olo * (int64_t)eout;
-    const bool out_dense = (int64_t)(ohi - olo + 1) == ocnt;
-    // Small calls (the reference's own bench shapes: benches/ndrustfft.rs:6-7, n x n with n = 128 ... 264): no DMA at all.  The kernels read the
-    // input straight from a pinned, device-mapped bounce buffer over PCIe and write the output into another one: two host memcpys and ONE stream
-    // synchronisation are the whole call (the plain path below pays two synchronous hipMemcpy of pageable memory, ~15-20 us each whatever the size).
-    const size_t small_limit = (size_t)NDFFT_DEV_INT("NDFFT_HOST_SMALL_KB", 2048) << 10;
-    if (ibytes + obytes <= small_limit) {
-        if ((rc = ws.bounce_in[0].reserve(std::max(ibytes, small_limit))) || (rc = ws.bounce_out[0].reserve(std::max(obytes, small_limit)))) return rc;
-        memcpy(ws.bounce_in[0].p, hin, ibytes);
-        const char *din = (const char *)ws.bounce_in[0].p - ilo * (int64_t)ein;
-        char *dout = (char *)ws.bounce_out[0].p - olo * (int64_t)eout;
-        rc = dispatch_peeled(P, din, dout, ein, eout, (hipStream_t) nullptr);
-        const hipError_t se = hipStreamSynchronize(nullptr);
-        if (rc) return rc;
-        if (se != hipSuccess) return fail(NDFFT_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
-        if (out_dense) memcpy(hout, ws.bounce_out[0].p, obytes);
-        else copy_view_elements((char *)out, (const char *)ws.bounce_out[0].p - olo * (int64_t)eout, ndim, shape_out, stride_out, eout);   // holes belong to the caller
-        return NDFFT_OK;
-    }
-    if ((rc = ws.stage_in.reserve(ibytes))) return rc;
-    if ((rc = ws.stage_out.reserve(obytes))) return rc;
-    // dense, C-ordered in dimension 0, transform along another axis: pipelined row chunks -- straight DMA for pinned arrays
-    // (ndfft_host_alloc), through pinned bounce buffers filled by the copy pool for pageable ones.  NDFFT_HOST_PIPE=0: plain path.
-    if (ndim >= 2 && axis != 0 && ilo == 0 && olo == 0 && shape_in[0] == shape_out[0] && shape_in[0] >= 16 &&
-        out_dense && ibytes + obytes >= ((size_t)8 << 20)) {
-        const int64_t isp = inner_span(ndim, shape_in, stride_in), osp = inner_span(ndim, shape_out, stride_out);
-        if (isp > 0 && osp > 0 && stride_in[0] >= isp && stride_out[0] >= osp) {
-            // a chunk must stay a real problem: kernel choice depends on the size of a call (hiprtc specialisation from 2^16-2^17
-            // points), so never cut below 2^18 points per chunk
-            const int64_t max_chunks = std::max<int64_t>(1, (P.nlanes * std::max(P.xlen, P.ylen)) >> 18);
-            // the caller's own arrays, seen before: registered once, DMA straight from / to them from then on.  The cache is asked FIRST
-            // (held = a registration it owns, kept alive for this call); only an array it does not own can be the caller's pinned memory
-            bool retry_unpinned = false;
-            {
-                HostPin pin_in(hin, ibytes), pin_out(hout, obytes);
-                const bool own_in = !pin_in.held && is_pinned(in), own_out = !pin_out.held && is_pinned(out);
-                if ((own_in || pin_in.held) && (own_out || pin_out.held)) {
-                    const int chunks = (int)std::min<int64_t>(std::min<int64_t>(shape_in[0], max_chunks), 8);
-                    const int rcp = exec_pinned_pipeline(ws, plan, op, hin, hout, ndim, shape_in, stride_in, shape_out, stride_out, axis, norm, scale, ein, eout, chunks);
-                    // A registration made by the cache can be stale: the caller freed the array and the allocator handed the same addresses out
-                    // again (seen on the MI355X with numpy arrays: hipMemcpyAsync then fails with "invalid argument" -- before anything has been
-                    // written to the caller's output).  Forget both ranges and run this call through the bounce buffers instead.
-                    if (rcp == NDFFT_OK || rcp != NDFFT_ERR_HIP || !(pin_in.held || pin_out.held)) return rcp;
-                    retry_unpinned = true;
-                }
-            }
-            if (retry_unpinned) {
-                (void)hipGetLastError();
-                HostRegCache::get().forget(hin); HostRegCache::get().forget(hout);
-                clear_err();
-            }
-            const int hp = sw().host_pipe;                    // NDFFT_HOST_PIPE
-            const bool force = hp == 1;                       // tests: pipeline small calls too
-            if (force || (hp != 0 && max_chunks >= 4 && ibytes + obytes >= ((size_t)32 << 20))) {   // small calls: the plain path
-                // chunks of ~32 MiB per direction (at least 4, at most 64)
-                const int64_t want = std::max<int64_t>(4, std::min<int64_t>(64, (int64_t)(std::max(ibytes, obytes) >> 25)));
-                const int chunks = (int)std::min<int64_t>(std::min<int64_t>(shape_in[0], force ? 64 : max_chunks), want);
-                return exec_bounce_pipeline(ws, plan, op, hin, hout, ndim, shape_in, stride_in, shape_out, stride_out, axis, norm, scale, ein, eout, chunks);
-            }
-        }
-    }
-    if (!out_dense && (rc = ws.bounce_out[0].reserve(obytes))) return rc;   // before anything is in flight
-    // (a copy that fails may have met a stale cached registration over the caller's array -- see HostRegCache: forget it and try once more)
-    auto copy_host = [](void *dst, const void *src, size_t bytes, hipMemcpyKind kind, const void *host_side) -> int {
-        if (hipMemcpy(dst, src, bytes, kind) == hipSuccess) return NDFFT_OK;
-        (void)hipGetLastError();
-        if (!HostRegCache::get().forget(host_side)) return fail(NDFFT_ERR_HIP, "hipMemcpy between the caller's array and the device failed");
-        NDFFT_HIP(hipMemcpy(dst, src, bytes, kind));
-        return NDFFT_OK;
-    };
-    if ((rc = copy_host(ws.stage_in.p, hin, ibytes, hipMemcpyHostToDevice, hin))) return rc;
-    const char *din = (const char *)ws.stage_in.p - ilo * (int64_t)ein;
-    char *dout = (char *)ws.stage_out.p - olo * (int64_t)eout;
-    rc = dispatch_peeled(P, din, dout, ein, eout, (hipStream_t) nullptr);
-    if (rc) { (void)hipStreamSynchronize(nullptr); return rc; }
-    if (out_dense) {
-        if ((rc = copy_host(hout, ws.stage_out.p, obytes, hipMemcpyDeviceToHost, hout))) return rc;   // synchronises with the kernel
-    } else {
-        // The output view has holes.  They belong to the caller (possibly to ANOTHER thread's &mut view of the same
-        // allocation), so they are neither read nor written: the span comes back into a private pinned image and only
-        // the view's own elements are copied out of it.
-        NDFFT_HIP(hipMemcpy(ws.bounce_out[0].p, ws.stage_out.p, obytes, hipMemcpyDeviceToHost));
-        copy_view_elements((char *)out, (const char *)ws.bounce_out[0].p - olo * (int64_t)eout, ndim, shape_out, stride_out, eout);
-    }
-    return NDFFT_OK;
-}
-
-int ndfft_host_reg_cache(size_t max_bytes) {
-    clear_err();
-    HostRegCache::get().set_limit(max_bytes);
-    return NDFFT_OK;
-}
-
-int ndfft_host_forget(const void *h_ptr) {
-    clear_err();
-    (void)HostRegCache::get().forget(h_ptr);
-    return NDFFT_OK;
 }
 
 int ndfft_last_input_policy(void) { return g_last_policy; }
@@ -1810,3 +1170,9 @@ int ndfft_release_workspace(void) {
 }
 
 }  // extern "C"
+
+// host.hip is a unit of its own (-DNDFFT_HOST_UNIT, set by every build list that names it).  A list of objects written before it
+// existed does not name it and would link a library without ndfft_exec: such a build gets the host-array call through this unit.
+#ifndef NDFFT_HOST_UNIT
+#include "host.hip"
+#endif

@@ -441,7 +441,7 @@ template <typename T, int F, int TPL, int LPB, typename RL, int OP, bool COL = f
                 if (a.vec_in) {                      // 2 doubles / 4 floats per 16-byte load
                     constexpr int W = 16 / sizeof(T);
                     const int nv = a.n_in / W;
-                    // (stream_in: the input comes from HBM, not from the Infinity Cache -- exec.hip: MallModel)
+                    // (stream_in: the input comes from HBM, not from the Infinity Cache -- exec_internal.h: MallModel)
                     if (a.stream_in) stage_loop<TPL>(t, nv, [&](int j) { return __builtin_nontemporal_load((const vec4f *)in + j); }, [&](int j, vec4f v) { ((vec4f *)raw)[j] = v; });
                     else stage_loop<TPL>(t, nv, [&](int j) { return ((const vec4f *)in)[j]; }, [&](int j, vec4f v) { ((vec4f *)raw)[j] = v; });
                     for (int j = W * nv + t; j < a.n_in; j += TPL) raw[j] = in[j];

@@ -124,17 +124,6 @@ int collect(std::vector<std::future<TaskResult>> &fs) {
     return NDFFT_OK;
 }
 
-// lowest / highest element offset of a view relative to its element 0
-void span_of(int ndim, const int64_t *shape, const int64_t *stride, int64_t &lo, int64_t &hi, int64_t &count) {
-    lo = hi = 0; count = 1;
-    for (int d = 0; d < ndim; ++d) {
-        count *= shape[d];
-        if (shape[d] <= 0) continue;
-        const int64_t e = (shape[d] - 1) * stride[d];
-        if (e < 0) lo += e; else hi += e;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // device-resident arrays: what a worker thread (bound to device `dev`) needs to move a block between the device
 // that holds the array (`root`) and its own device without ever touching an element the block does not own
@@ -308,7 +297,7 @@ TaskResult run_remote_block(const RemoteBlock &b) {
         std::vector<int64_t> sh(shape);
         if (d >= 0) sh[d] = e;
         Side s; int64_t hi;
-        span_of(ndim, sh.data(), stride.data(), s.lo, hi, s.count);
+        view_range(ndim, sh.data(), stride.data(), s.lo, hi, s.count);
         s.span = hi - s.lo + 1;
         s.packed = s.span > s.count;
         return s;

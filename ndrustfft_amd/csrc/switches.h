@@ -48,7 +48,7 @@ struct Switches {
     int rfs_logn1 = 0;                   // NDFFT_RFS_LOGN1: 7..11 forces the real four-step's split n = 2^a * N2
     int cs_chunk_mb = 144;               // NDFFT_CS_CHUNK_MB: column four-step chunk (0 = one chunk)
     int stream_loads = -1;               // NDFFT_STREAM_LOADS: 0 / 1 forces the load policy of the dense C2C row kernels (default: the residency model)
-    // ---- host arrays (exec.hip)
+    // ---- host arrays (host.hip)
     int host_pipe = -1;                  // NDFFT_HOST_PIPE: 0 = never chunk-pipeline host calls, 1 = always (default: from 32 MiB)
     long host_reg_cache_mb = 0;          // NDFFT_HOST_REG_CACHE_MB: initial budget of the opt-in registration cache (ndfft_host_reg_cache)
     int copy_threads = 0;                // NDFFT_COPY_THREADS: size of the host copy pool (default: 3/4 of the usable CPUs, 2..12)

@@ -151,6 +151,18 @@ bool emul_host_registered(const void *p) {
     for (auto &kv : g_reg) if ((const char *)p >= kv.first && (const char *)p < kv.first + kv.second) return true;
     return false;
 }
+// test hook: host <-> device copies issued since the last reset, as {hipMemcpy H2D, hipMemcpy D2H, hipMemcpyAsync H2D, hipMemcpyAsync D2H,
+// hipMemcpyAsync whose host side lies in a registered range} -- which strategy ndfft_exec took for a call (tests/test_emul_parity.py: test_host_route_table)
+namespace { std::atomic<long long> g_copies[5]; }
+void emul_count_copy(const void *d, const void *s, hipMemcpyKind k, bool async) {
+    if (k != hipMemcpyHostToDevice && k != hipMemcpyDeviceToHost) return;
+    const bool h2d = k == hipMemcpyHostToDevice;
+    ++g_copies[(async ? 2 : 0) + (h2d ? 0 : 1)];
+    if (async && emul_host_registered(h2d ? s : d)) ++g_copies[4];
+}
+extern "C" void emul_copy_counts(long long *out, int reset) {
+    for (int i = 0; i < 5; ++i) { if (out) out[i] = g_copies[i].load(); if (reset) g_copies[i] = 0; }
+}
 extern "C" int emul_is_registered(const void *p) { return emul_host_registered(p) ? 1 : 0; }
 extern "C" size_t emul_host_registered_bytes() {
     std::lock_guard<std::mutex> g(g_reg_mu);

@@ -53,11 +53,13 @@ hipError_t hipFree(void *p);
 // host <-> device copies must name memory of the CURRENT device: the library keeps one workspace per device, and a
 // staging buffer of device 0 showing up while device 1 is current is exactly the bug class this catches
 void emul_check_current(const void *devptr, const char *what);
-inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) {
+void emul_count_copy(const void *d, const void *s, hipMemcpyKind k, bool async);   // emul_runtime.cpp: test counters of host <-> device copies
+inline hipError_t emul_memcpy(void *d, const void *s, size_t n, hipMemcpyKind k) {
     if (k == hipMemcpyHostToDevice) emul_check_current(d, "hipMemcpy H2D");
     if (k == hipMemcpyDeviceToHost) emul_check_current(s, "hipMemcpy D2H");
     memcpy(d, s, n); return 0;
 }
+inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { emul_count_copy(d, s, k, false); return emul_memcpy(d, s, n, k); }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 inline hipError_t hipDeviceSynchronize() { return 0; }
 // pinned-host pipeline of ndfft_exec: never taken in the emulation (no pointer is ever "pinned"), stubs only
@@ -89,7 +91,11 @@ hipError_t hipDeviceCanAccessPeer(int *can, int dev, int peer);
 hipError_t hipDeviceEnablePeerAccess(int peer, unsigned flags);
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
 bool emul_copy_should_fail(const void *a, const void *b);   // emul_runtime.cpp: injected failures of copies on registered host ranges
-inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t) { if (emul_copy_should_fail(d, s)) return 1; return hipMemcpy(d, s, n, k); }
+inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t) {
+    emul_count_copy(d, s, k, true);            // (a copy that is made to fail was still issued: it counts)
+    if (emul_copy_should_fail(d, s)) return 1;
+    return emul_memcpy(d, s, n, k);
+}
 inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
 inline hipError_t hipHostFree(void *p) { free(p); return 0; }
 enum { hipHostRegisterDefault = 0 };

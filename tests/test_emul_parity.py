@@ -85,7 +85,7 @@ def test_sharded_fft2_on_three_devices(L, monkeypatch):
 
 def test_baseline_length_fixtures(L, blvec): ps.baseline_length_fixtures(L, blvec)
 def test_infinity_cache_residency_model(L):
-    """exec.hip: MallModel through ndfft_last_input_policy (device-resident arrays on the emulation): an unknown input keeps the size rule (plain loads); a re-read
+    """exec_internal.h: MallModel through ndfft_last_input_policy (device-resident arrays on the emulation): an unknown input keeps the size rule (plain loads); a re-read
     input is worth plain loads while its reuse distance fits the cache; an output of more than 64 MiB was written with nt stores and is cold (streaming) when it
     becomes an input; a rotation of inputs larger than the cache streams every member; a small output stays resident; ndfft_set_input_hint overrides."""
     import ctypes
@@ -212,6 +212,84 @@ def test_host_registration_cache_keeps_hot_arrays_and_retries_stale_ones(L):
         L.c.emul_fail_registered_copies(0)
         L.check(L.c.ndfft_host_reg_cache(0))
     assert L.c.emul_host_registered_bytes() == 0
+
+
+# ndfft_exec's strategy per kind of call (host.hip), told apart by the host <-> device copies each one issues: (label, switches, op, shape, axis, real dtype,
+# (hipMemcpy H2D, hipMemcpy D2H, hipMemcpyAsync H2D, hipMemcpyAsync D2H, hipMemcpyAsync on a registered range)).  All arrays are pageable, the registration cache is off.
+SMALL, PLAIN, BOUNCE4 = (0, 0, 0, 0, 0), (1, 1, 0, 0, 0), (0, 0, 4, 4, 0)
+HOST_ROUTE_TABLE = [
+    ("small",                {},                          "ndfft",     (64, 128),     1, np.float64, SMALL),      # 256 KiB: mapped bounce buffers, no copy call at all
+    ("axis 0",               {},                          "ndfft",     (300, 1024),   0, np.float64, PLAIN),      # 9.4 MiB, but dimension 0 is the transform's
+    ("under 8 MiB",          {},                          "ndfft",     (200, 1024),   1, np.float64, PLAIN),
+    ("under 32 MiB",         {},                          "ndfft",     (520, 1024),   1, np.float64, PLAIN),      # 2^19 points: max_chunks = 2 < 4
+    ("NDFFT_HOST_PIPE=1",    {"NDFFT_HOST_PIPE": "1"},    "ndfft",     (520, 1024),   1, np.float64, BOUNCE4),
+    ("NDFFT_HOST_PIPE=0",    {"NDFFT_HOST_PIPE": "0"},    "ndfft",     (520, 1024),   1, np.float64, PLAIN),
+    ("r2c, bounce",          {"NDFFT_HOST_PIPE": "1"},    "ndfft_r2c", (600, 1024),   1, np.float64, BOUNCE4),    # shape_in != shape_out
+    ("dct2 3-D, bounce",     {"NDFFT_HOST_PIPE": "1"},    "nddct2",    (70, 96, 128), 1, np.float64, BOUNCE4),
+]
+
+
+def test_host_route_table(L):
+    """host.hip's strategy choice, pinned by the copies each strategy issues (the emulation counts them): host_small none, host_plain one synchronous
+    hipMemcpy per direction, host_bounce one hipMemcpyAsync per chunk and direction on its own pinned slots, host_pinned the same straight on the
+    caller's registered arrays; a copy that fails on a cache-held registration is followed by the next strategy in line.  Results against the oracle."""
+    import ctypes
+    import synth
+    from helpers import TOL, assert_close, cdt_of
+    from ndrustfft_amd import api, handlers
+    from oracle import oracle_ctypes as orc
+    def counts(reset=False):
+        c = (ctypes.c_longlong * 5)(); L.c.emul_copy_counts(c, 1 if reset else 0); return tuple(c)
+    def counted(call):
+        counts(reset=True); call(); return counts()
+    got = []
+    for label, env, name, shape, axis, rdt, want in HOST_ROUTE_TABLE:
+        fn, ofn, _, in_c, out_c = ps.OPS[name]
+        sin, sout = ps.shapes_for(name, shape, axis)
+        x = ps.make_input(name, sin, rdt); y = np.zeros(sout, cdt_of(rdt) if out_c else rdt); yo = np.zeros_like(y)
+        h, o = ps.handlers_for(name, shape[axis], rdt, L)
+        with ps.switches(L, **env):
+            fn(x, y, h, axis); y[...] = 0                                   # (the plan's tables go up on its first call: not counted)
+            got.append((label, counted(lambda: fn(x, y, h, axis)), want))
+        ofn(x, yo, o, axis)
+        assert_close(y, yo, axis, TOL[np.dtype(rdt)], f"host route {label}")
+    # output views with holes: every element outside the view keeps its sentinel
+    # (384 KiB: host_small; 6 MiB: host_plain, whose private image of the holed output comes back with one synchronous D2H copy like a dense one)
+    for label, rows, want in (("small, stepped output", 64, SMALL), ("plain, stepped output", 1024, PLAIN)):
+        n = 128; h = handlers.FftHandler(n, _library=L)
+        x = synth.complex_array((rows, n)); yb = np.full((rows, 2 * n), 7.0 - 3.0j); y = yb[:, ::2]; yo = np.zeros((rows, n), np.complex128)
+        api.ndfft(x, y, h, 1); y[...] = 0
+        got.append((label, counted(lambda: api.ndfft(x, y, h, 1)), want))
+        orc.ndfft(x, yo, orc.FftHandler(n), 1)
+        assert_close(y, yo, 1, TOL[np.dtype(np.float64)], f"host route {label}"); assert np.all(yb[:, 1::2] == 7.0 - 3.0j), label
+    # the registration cache: the second sighting registers both arrays, from then on the calls run the direct pipeline on them
+    isreg = lambda a: bool(L.c.emul_is_registered(ctypes.c_void_p(a.ctypes.data)))
+    n = 1024; h = handlers.FftHandler(n, _library=L)
+    x = synth.complex_array((520, n)); y = np.zeros_like(x); yo = np.zeros_like(x); orc.ndfft(x, yo, orc.FftHandler(n), 1)
+    def call(): y[...] = 0; api.ndfft(x, y, h, 1)
+    def check(label): assert_close(y, yo, 1, TOL[np.dtype(np.float64)], f"host route {label}")
+    L.check(L.c.ndfft_host_reg_cache(4 * x.nbytes))
+    try:
+        call(); call()
+        got.append(("registered, third call", counted(call), (0, 0, 2, 2, 4))); check("registered")     # min(max_chunks = 2, 8) chunks
+        assert isreg(x) and isreg(y)
+        # a stale registration: the first copy of the direct pipeline fails, both ranges are forgotten and the next strategy in line finishes the call --
+        # at this size with default switches that is the plain one (max_chunks = 2: no bounce pipeline), with NDFFT_HOST_PIPE=1 the bounce pipeline
+        L.c.emul_fail_registered_copies(1)
+        got.append(("stale registration", counted(call), (1, 1, 1, 0, 1))); check("stale -> plain")
+        L.c.emul_fail_registered_copies(0)
+        assert not isreg(x) and not isreg(y), "the failing ranges were not forgotten"
+        call(); call(); assert isreg(x) and isreg(y)                        # registrable again: first sighting, second sighting
+        with ps.switches(L, NDFFT_HOST_PIPE="1"):
+            L.c.emul_fail_registered_copies(1)
+            got.append(("stale registration, NDFFT_HOST_PIPE=1", counted(call), (0, 0, 5, 4, 1))); check("stale -> bounce")
+            L.c.emul_fail_registered_copies(0)
+        assert not isreg(x) and not isreg(y), "the failing ranges were not forgotten"
+    finally:
+        L.c.emul_fail_registered_copies(0)
+        L.check(L.c.ndfft_host_reg_cache(0))
+    bad = [g for g in got if g[1] != g[2]]
+    assert not bad, bad
 
 
 def test_interleaved_mut_views(L): ps.interleaved_mut_views_two_threads(L, rounds=1)
