@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 
+import accuracy as acc
 import synth
 from helpers import TOL, assert_close, cdt_of
 from ndrustfft_amd import _lib, api, handlers
@@ -1144,3 +1145,243 @@ def handler_clone_shares_plan(L):
     x = synth.complex_array((2, 16)); y = np.zeros_like(x)
     api.ndfft(x, y, h2, 1)
     assert_close(y, np.fft.fft(x, axis=1), 1, 1e-10, "cloned handler")
+
+
+# ---- working-precision accuracy and lane isolation (tests/accuracy.py, docs/accuracy.md) --------------------------------------
+# A case is a ROUTE_TABLE row: (switches, op, shape, axis, real dtype, layout, route) -- route: the last_path() the case must take, a tuple
+# of admissible ones, or None (recorded only).
+ACC_FACTOR = 3.0      # e(library) <= ACC_FACTOR * max(e(oracle, this input), e(oracle, U[-1,1) input)): docs/accuracy.md derives the 3
+
+
+def _acc_call(L, name, x, sout, odt, h, axis, layout, transform=None):
+    y = np.zeros(sout, odt, order="F" if layout == "F" else "C")
+    if layout == "F":
+        x = np.asfortranarray(x)
+    if transform is not None:
+        return transform(name, x, y, h, axis), L.last_path()
+    OPS[name][0](x, y, h, axis)
+    return y, L.last_path()
+
+
+def accuracy_records(L, case, kinds=acc.INPUTS, transform=None):
+    """One case on every input kind: the library and the oracle (same dtype, same input) against the truth of tests/accuracy.py.  Returns one
+    record per input: route, op, shape, dtype, input, e_l2 / e_bin of the library and of the oracle, the bar's denominators and the ratios."""
+    env, name, shape, axis, rdt, layout, want = case
+    n = shape[axis]
+    sin, sout = shapes_for(name, shape, axis)
+    odt = cdt_of(rdt) if OPS[name][4] else np.dtype(rdt)
+    assert kinds[0] == "uniform"                         # (its oracle error is the second term of every bar)
+    recs = []
+    with switches(L, **env):
+        h, o = handlers_for(name, n, rdt, L)
+        for kind in kinds:
+            x = acc.make_input(kind, name, sin, axis, rdt, offset=n)
+            y, path = _acc_call(L, name, x, sout, odt, h, axis, layout, transform)
+            yo = np.zeros(sout, odt); OPS[name][1](x, yo, o, axis)
+            t = acc.prepare(acc.truth(name, x, n, axis), axis)
+            lib = acc.errors(y, t, axis, rdt); orac = acc.errors(yo, t, axis, rdt)
+            if kind == "uniform":
+                uni = orac
+            den = tuple(max(a, b) for a, b in zip(orac, uni))
+            ratio = tuple((l / d if d > 0 else (0.0 if l == 0 else float("inf"))) if l == l else float("nan") for l, d in zip(lib, den))
+            recs.append({"route": path, "want": want, "op": name, "shape": tuple(shape), "axis": axis, "n": n, "dtype": np.dtype(rdt).name, "input": kind,
+                         "switches": dict(env), "lib": lib, "oracle": orac, "den": den, "ratio": ratio})
+    return recs
+
+
+def _route_ok(path, want):
+    return want is None or path == want or (isinstance(want, tuple) and path in want)
+
+
+def accuracy_routes(L, cases, kinds=acc.INPUTS, transform=None, verbose=False):
+    """Every case within ACC_FACTOR of the oracle's own error, both metrics, every input; and on the route it names.  Returns (routes seen, records)."""
+    bad, seen, records = [], set(), []
+    for case in cases:
+        for r in accuracy_records(L, case, kinds, transform):
+            records.append(r); seen.add(r["route"])
+            line = (f"{r['route']} {r['op']} {r['shape']} axis={r['axis']} {r['dtype']} {r['input']} {r['switches'] or ''}: e_l2 {r['lib'][0]:.3f} eps (oracle {r['den'][0]:.3f}, ratio {r['ratio'][0]:.2f}), "
+                    f"e_bin {r['lib'][1]:.3f} eps (oracle {r['den'][1]:.3f}, ratio {r['ratio'][1]:.2f})")
+            if verbose:
+                print(line, flush=True)
+            if not _route_ok(r["route"], r["want"]):
+                bad.append(f"route {r['route']} instead of {r['want']}: " + line)
+            if not all(l <= ACC_FACTOR * d for l, d in zip(r["lib"], r["den"])):      # (nan fails)
+                bad.append("beyond the bar: " + line)
+    assert not bad, "\n".join([f"{len(bad)} accuracy failures"] + bad)
+    return seen, records
+
+
+def lane_isolation(L, cases, transform=None):
+    """Lanes are numerically independent: the kept lanes ({0, middle, last, every 5th}) come out bit-identical whether the other lanes hold U[-1,1),
+    the same scaled by 1e30 (f32) / 1e250 (f64), or NaN -- on the same route."""
+    bad = []
+    for env, name, shape, axis, rdt, layout, want in cases:
+        n = shape[axis]
+        sin, sout = shapes_for(name, shape, axis)
+        odt = cdt_of(rdt) if OPS[name][4] else np.dtype(rdt)
+        other = tuple(s for d, s in enumerate(sin) if d != axis)
+        keep = acc.kept_lanes(int(np.prod(other)))
+        km = np.expand_dims(keep.reshape(other), axis)
+        x = acc.make_input("uniform", name, sin, axis, rdt, offset=n)
+        big = np.dtype(rdt).type(1e30 if np.dtype(rdt) == np.float32 else 1e250)
+        xs = (x, (x * np.where(km, np.dtype(rdt).type(1), big)).astype(x.dtype), np.where(km, x, complex(np.nan, np.nan) if np.iscomplexobj(x) else np.nan).astype(x.dtype))
+        with switches(L, **env):
+            h, _ = handlers_for(name, n, rdt, L)
+            outs = [_acc_call(L, name, xi, sout, odt, h, axis, layout, transform) for xi in xs]
+        lanes = [np.moveaxis(y, axis, -1).reshape(keep.size, -1)[keep] for y, _ in outs]
+        what = f"{name} {shape} axis={axis} {np.dtype(rdt).name} {env or ''} routes {[p for _, p in outs]}"
+        if len({p for _, p in outs}) != 1:
+            bad.append("route changed: " + what)
+        if not np.isfinite(lanes[0]).all():
+            bad.append("non-finite output of a finite lane: " + what)
+        for k, label in ((1, "scaled"), (2, "NaN")):
+            if not np.array_equal(lanes[0], lanes[k]):
+                rows = np.nonzero((lanes[0] != lanes[k]).any(axis=1))[0]
+                bad.append(f"kept lanes differ with {label} neighbours (kept-lane rows {rows[:8].tolist()}): " + what)
+    assert not bad, "\n".join([f"{len(bad)} lane-isolation failures"] + bad)
+
+
+# ---- the case table of the MI355X run: every kernel route, and within the routes the forms listed in docs/accuracy.md ------------------------
+F64, F32 = np.float64, np.float32
+BOTH = (F64, F32)
+REAL6 = ("ndfft_r2c", "ndifft_r2c", "nddct1", "nddct2", "nddct3", "nddct4")
+ACC_REQUIRED_ROUTES = {"wave_reg", "tiny_row", "tiny_col", "tinymat_row", "tinymat_col", "reg_row", "reg_col", "regreal_row", "regreal_col",
+                       "pow2_reg", "pow2_real", "pow2_col", "col_split", "jit_reg", "jit_real", "jit_col", "plain_real", "plain_col",
+                       "rader_reg", "rader_col", "blue_reg", "blue_col", "blue_global", "generic_row", "generic_col",
+                       "four_step", "real_four_step", "transpose+pow2_reg"}
+
+
+def _c2c(shape, axis, want, dts=BOTH, env=None, layout="C"):
+    return [(env or {}, name, shape, axis, rdt, layout, want) for rdt in dts for name in ("ndfft", "ndifft")]
+
+
+def _real(F, lanes, want, dts=BOTH, env=None, ops=REAL6, col=False, outer=None):
+    """The real ops whose inner FFT has F points (n = 2 F; DCT-I: n = F + 1) on `lanes` rows, or as columns of an (n, lanes) / (outer, n, lanes) array."""
+    out = []
+    for rdt in dts:
+        for name in ops:
+            n = F + 1 if name == "nddct1" else 2 * F
+            shape, axis = ((lanes, n), 1) if not col else (((n, lanes), 0) if outer is None else ((outer, n, lanes), 1))
+            out.append((env or {}, name, shape, axis, rdt, "C", want))
+    return out
+
+
+def _one(name, shape, axis, rdt, want, env=None, layout="C"):
+    return [(env or {}, name, shape, axis, rdt, layout, want)]
+
+
+def acc_cases_short():
+    """Wavefront, thread-per-lane (tiny, tinymat, RegFft2, RegReal) and the generic LDS kernel."""
+    c = []
+    for n in (8, 64):
+        c += _c2c((37, n), 1, "wave_reg")
+    c += _c2c((37, 16), 1, "tiny_row", env={"NDFFT_WAVE": "0"}) + _c2c((777, 7), 1, "tiny_row")
+    c += _c2c((3, 7, 70), 1, "tiny_col") + _c2c((40, 7), 1, "tiny_col", layout="F")
+    for rdt in BOTH:
+        for name in REAL6:
+            c += _one(name, (300, 12), 1, rdt, "tinymat_row") + _one(name, (300, 16), 1, rdt, "tinymat_row") + _one(name, (9, 12, 70), 1, rdt, "tinymat_col")
+    c += _c2c((3, 1000), 1, "generic_row")
+    c += _c2c((517, 97), 1, "generic_row", dts=(F64,), env={"NDFFT_RADER": "0", "NDFFT_BLUE": "0"})
+    c += _c2c((97, 40), 0, "generic_col", env={"NDFFT_RADER": "0", "NDFFT_BLUE": "0"})
+    c += _real(500, 3, "generic_row") + _real(24, 40, "generic_col", dts=(F64,), env={"NDFFT_TINY": "0"}, col=True)
+    for n in (17, 19, 23, 29, 31, 62, 63):                                  # RegFft2 (reg_lanes's shapes)
+        rows = (1 << 16) // n + 37
+        c += _c2c((rows, n), 1, "reg_row")
+        if n in (19, 31, 62):
+            c += _c2c((5, n, rows // 4), 1, "reg_col")
+    for n, dts in ((40, (F64,)), (48, (F64,)), (72, (F32,))):               # RegReal: the AGPR-spill sizes of f64, the longest f32 lane
+        rows = (1 << 16) // n + 29
+        for rdt in dts:
+            for name in REAL6:
+                inner_prime = name == "nddct1" and n != 40        # (DCT-I's inner FFT has n - 1 points: 47 and 71 are primes beyond RegReal's butterflies -- any route)
+                c += _one(name, (rows, n), 1, rdt, None if inner_prime else "regreal_row")
+                if n != 40:
+                    c += _one(name, (3, n, rows // 2), 1, rdt, None if inner_prime else "regreal_col")
+    return c
+
+
+def acc_cases_pow2():
+    """The ahead-of-time power-of-two kernels: long rows (twiddle rebuild passes n >= 4096, f32 PSPLIT), real-op rows, column tiles, column four-step."""
+    c = []
+    for n in (4096, 8192, 16384):
+        c += _c2c((37, n), 1, "pow2_reg")
+    for F in (4096, 8192):
+        c += _real(F, 5, "pow2_real")
+    c += _real(1024, 40, "pow2_col", col=True, ops=tuple(o for o in REAL6 if o != "ndifft_r2c")) + _real(1024, 40, "pow2_col", dts=(F64,), col=True, ops=("ndifft_r2c",))
+    c += _real(1024, 40, "col_split", dts=(F32,), col=True, ops=("ndifft_r2c",))        # (f32 C2R lanes of 2048 points: the column four-step)
+    c += _c2c((1024, 40), 0, "pow2_col") + _c2c((2048, 200), 0, "pow2_col", dts=(F64,))
+    c += _one("ndfft_r2c", (4096, 70), 0, F64, "pow2_col")
+    c += _c2c((4096, 16), 0, "col_split") + _one("ndifft_r2c", (8192, 40), 0, F32, "col_split") + _one("ndfft_r2c", (8192, 21), 0, F64, "col_split")
+    c += _one("ndfft_r2c", (8192, 64), 0, F32, "col_split") + _one("ndifft_r2c", (8192, 48), 0, F64, "col_split")
+    c += _c2c((4096, 24), 0, "transpose+pow2_reg", dts=(F64,), env={"NDFFT_COLSPLIT": "0"})
+    c += _one("nddct2", (4096, 64), 0, F64, "transpose+pow2_real") + _one("ndifft_r2c", (4096, 64), 0, F64, "pow2_col_xcd")
+    return c
+
+
+def acc_cases_jit():
+    """hiprtc-specialised smooth lengths: partial-round recipes, f32 half-thread vector rows, real ops, column tiles, odd real lengths (plain_kernel.h)."""
+    c = []
+    for n in (264, 840, 1008):
+        c += _c2c(((1 << 17) // n + 7, n), 1, "jit_reg")
+    for n in (432, 1000):
+        c += _c2c((max(64, (1 << 18) // n), n), 1, "jit_reg", dts=(F32,))
+    c += _real(264, (1 << 16) // 264 + 5, "jit_real")
+    c += _c2c((264, (1 << 16) // 264 + 8), 0, "jit_col") + _real(264, (1 << 16) // 264 + 8, "jit_col", ops=("ndfft_r2c", "nddct2", "nddct1"), col=True)
+    for n in (63, 1001, 3003):
+        rows = (1 << 17) // n + 5
+        for rdt in BOTH:
+            for name in ("ndfft_r2c", "ndifft_r2c", "nddct2", "nddct3", "nddct4"):
+                c += _one(name, (rows, n), 1, rdt, ("plain_real", "regreal_row") if n == 63 else "plain_real")
+    for name in ("ndfft_r2c", "nddct2"):
+        c += _one(name, (63, (1 << 17) // 63 + 8), 0, F64, ("plain_col", "regreal_col", "transpose+plain_real"))
+    c += _one("ndfft_r2c", (45, 2920), 0, F64, "plain_col", env={"NDFFT_TINY": "0"})
+    return c
+
+
+def acc_cases_rader():
+    """Rader / Good-Thomas: radix 17..31 passes, two-factor cofactors, beyond Bluestein's reach, the symmetric and half-length DCT-I forms, column tiles."""
+    c = []
+    for F, dts, full in ((97, BOTH, True), (103, BOTH, False), (139, BOTH, False), (233, (F64,), False), (311, BOTH, False),
+                         (306, BOTH, True), (513, BOTH, False), (2336, BOTH, False), (8191, BOTH, False)):
+        rows = (1 << 16) // F + 5
+        c += _c2c((rows, F), 1, "rader_reg", dts=dts)
+        c += _real(F, rows, "rader_reg", dts=dts, ops=REAL6 if full else ("ndifft_r2c", "nddct2"))
+    for n in (512, 1024, 2048, 128, 1010, 8192):       # DCT-I: n - 1 composite (symmetric form) / prime (half-length convolution)
+        for rdt in BOTH:
+            c += _one("nddct1", ((1 << 16) // (n - 1) + 3, n), 1, rdt, "rader_reg")
+    c += _c2c((97, 680), 0, "rader_col") + _one("ndifft_r2c", (97, 1000), 0, F64, "rader_col") + _one("nddct1", (512, 140), 0, F64, "rader_col")
+    return c
+
+
+def acc_cases_bluestein():
+    """Bluestein on the register kernel (13-smooth and power-of-two M), column tiles, and over global memory."""
+    c = []
+    env = {"NDFFT_RADER": "0"}
+    for F, M, full in ((263, 1024, True), (1283, 4096, False), (4093, 8192, False)):
+        rows = (1 << 17) // M + 5
+        c += _c2c((rows, F), 1, "blue_reg", env=env)
+        c += _real(F, rows, "blue_reg", env=env, ops=REAL6 if full else ("ndifft_r2c", "nddct2"))
+    c += _c2c((97, 520), 0, "blue_col", env=env)
+    c += _c2c((3, 4099), 1, "blue_global") + _one("nddct2", (3, 4099), 1, F64, "blue_global") + _one("ndfft_r2c", (3, 2 * 4099), 1, F64, "blue_global")
+    return c
+
+
+def acc_cases_long():
+    """Lanes beyond one workgroup: the complex four-step (power-of-two and hiprtc passes) and the real four-step, 1-3 lanes each."""
+    c = _c2c((2, 32768), 1, "four_step", dts=(F64,)) + _c2c((2, 1 << 20), 1, "four_step", dts=(F64,)) + _c2c((2, 196608), 1, "four_step", dts=(F64,))
+    c += _c2c((1, 1 << 22), 1, "four_step", dts=(F32,))
+    for name in REAL6:
+        c += _one(name, (2, (1 << 16) + (name == "nddct1")), 1, F64, "real_four_step")
+        c += _one(name, (2, (1 << 17) if name != "nddct1" else (1 << 16) + 1), 1, F32, "real_four_step")
+    c += _one("nddct2", (2, 196608), 1, F64, "real_four_step") + _one("nddct4", (3, 163840), 1, F64, "real_four_step")
+    return c
+
+
+ACC_GPU_FAMILIES = {"short": acc_cases_short, "pow2": acc_cases_pow2, "jit": acc_cases_jit, "rader": acc_cases_rader,
+                    "bluestein": acc_cases_bluestein, "long": acc_cases_long}
+
+
+def acc_gpu_cases(family, dt=None):
+    """The cases of one family, optionally of one dtype only ("f64" / "f32": the tests run the two apart to stay short)."""
+    want = {None: None, "f64": np.dtype(F64), "f32": np.dtype(F32)}[dt]
+    return [c for c in ACC_GPU_FAMILIES[family]() if want is None or np.dtype(c[4]) == want]

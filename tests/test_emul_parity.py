@@ -496,3 +496,24 @@ def test_route_table(L):
             assert_close(y, yo, 1, TOL[np.dtype(rdt)], f"{name} stepped n={n}")
     bad = [g for g in got if g[3] != g[4]]
     assert not bad, bad
+
+
+# working-precision accuracy and lane isolation (parity_suite.accuracy_routes / lane_isolation, docs/accuracy.md) on every route above, plus the long power-of-two
+# rows (twiddle rebuild passes), DCT-I lengths (the cancellation-prone fold) and the lengths the LDS kernel serves through Rader-free Bluestein / odd-n forms
+ACC_EXTRA = ([({}, "ndfft", (2, n), 1, rdt, "C", "pow2_reg") for n in (4096, 8192, 16384) for rdt in (np.float64, np.float32)] +
+             [({}, "nddct1", (3, n), 1, np.float64, "C", None) for n in (98, 129, 257, 513, 1025, 2049, 4097)] +
+             [({}, "nddct1", (3, n), 1, np.float32, "C", None) for n in (513, 4097)] +
+             [({}, "ndfft", (2, 8191), 1, np.float64, "C", None), ({}, "ndfft", (3, 263), 1, np.float64, "C", None),
+              ({}, "ndfft_r2c", (3, 1001), 1, np.float64, "C", None), ({}, "nddct2", (3, 1001), 1, np.float64, "C", None)])
+
+
+def test_accuracy_routes(L):
+    """Every route of ROUTE_TABLE and the ACC_EXTRA lengths within 3 x the oracle's own error against an 80-bit truth (f32: a float64 truth), lane L2 and
+    worst bin, on uniform, impulse and graded inputs.  The emulation is an -O1 x86 build without FMA contraction: it speaks for the tables and the
+    operation order, not for the gfx950 code (tests/test_gpu_parity.py does)."""
+    ps.accuracy_routes(L, ROUTE_TABLE + ACC_EXTRA)
+
+
+def test_lane_isolation(L):
+    """The kept lanes are bit-identical whatever the other lanes hold (huge values, NaN), on every route of ROUTE_TABLE and ACC_EXTRA."""
+    ps.lane_isolation(L, ROUTE_TABLE + ACC_EXTRA)

@@ -549,3 +549,54 @@ def test_jit_column_tiles_of_four_lanes(L):
         for norm in ("Default", "None"):
             assert ps.run_case(L, name, shape, axis, rdt, norm=norm) == want, (name, shape)
     assert ps.run_case(L, "nddct2", (4000, 40), 0, np.float64) != "jit_col"
+
+
+# ---- working precision: every kernel route within 3 x the oracle's own error against an 80-bit truth, and lanes independent (docs/accuracy.md) -------------
+_ACC_SEEN = {}      # family -> routes its accuracy test saw (test_accuracy_required_routes)
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("family", list(ps.ACC_GPU_FAMILIES))
+def test_accuracy_routes(L, family, dt):
+    """Lane L2 and worst bin, in eps, of every case of the family on uniform, impulse and graded inputs: e(library) <= 3 max(e(oracle), e(oracle on U[-1,1))),
+    the oracle measured here at the same dtype against the same truth; every case on the route it names.  Each figure is printed before the assertion."""
+    seen, _ = ps.accuracy_routes(L, ps.acc_gpu_cases(family, dt), verbose=True)
+    _ACC_SEEN[family, dt] = seen
+
+
+def _unaligned_device_transform(name, x, y, h, axis):
+    """The call on torch tensors whose base pointers are only 8-byte aligned (jit.hip compiles the plain-recipe variant for them)."""
+    import torch
+    tdt = torch.from_numpy(np.zeros(1, x.dtype)).dtype
+    buf = torch.zeros(x.size + 1, dtype=tdt, device="cuda:0"); out = torch.zeros(y.size + 1, dtype=tdt, device="cuda:0")
+    xd = buf[1:].view(*x.shape); yd = out[1:].view(*y.shape)
+    xd.copy_(torch.from_numpy(np.ascontiguousarray(x)))
+    assert xd.data_ptr() % 16 == 8 and yd.data_ptr() % 16 == 8
+    ps.OPS[name][0](xd, yd, h, axis)
+    torch.cuda.synchronize()
+    return yd.cpu().numpy()
+
+
+def test_accuracy_c64_rows_from_8_byte_aligned_base(L):
+    """f32 C2C rows of 1000 points from a base pointer that is only 8-byte aligned: the same bar, and the lanes stay independent."""
+    cases = [({}, name, (300, 1000), 1, np.float32, "C", "jit_reg") for name in ("ndfft", "ndifft")]
+    ps.accuracy_routes(L, cases, transform=_unaligned_device_transform, verbose=True)
+    ps.lane_isolation(L, cases, transform=_unaligned_device_transform)
+
+
+def test_accuracy_required_routes(L):
+    """The accuracy families together ran every kernel route (a family that has not run in this session runs here)."""
+    for family in ps.ACC_GPU_FAMILIES:
+        for dt in ("f64", "f32"):
+            if (family, dt) not in _ACC_SEEN:
+                _ACC_SEEN[family, dt] = ps.accuracy_routes(L, ps.acc_gpu_cases(family, dt))[0]
+    seen = set().union(*_ACC_SEEN.values())
+    assert ps.ACC_REQUIRED_ROUTES <= seen, sorted(ps.ACC_REQUIRED_ROUTES - seen)
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("family", list(ps.ACC_GPU_FAMILIES))
+def test_lane_isolation(L, family, dt):
+    """The kept lanes of every case come out bit-identical whether their neighbours hold U[-1,1), values 1e30 / 1e250 times larger, or NaN: no arithmetic
+    crosses lanes (wavefront swaps with the wrong bank mask, two lanes packed into one transform, a clamped tail load landing in a live register)."""
+    ps.lane_isolation(L, ps.acc_gpu_cases(family, dt))

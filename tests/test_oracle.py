@@ -4,6 +4,7 @@ three strategies, the three normalisation points and the restated panics."""
 import numpy as np
 import pytest
 
+import accuracy as acc
 import synth
 from helpers import GOLDEN_SIZES, assert_close, cdt_of, rel_global
 from oracle import oracle_ctypes as orc
@@ -193,6 +194,71 @@ def test_baseline_lengths_dct(blvec):
         getattr(orc, f"nddct{k}")(x, y, h, 1)
         assert_close(y, blvec[f"dct_f64_n512_dct{k}_np"], 1, 4e-12, f"dct{k} vs scipy")
         assert_close(y[:1], blvec[f"dct_f64_n512_dct{k}_ld"][None, :], 1, 4e-12, f"dct{k} vs long-double definition")
+
+
+# ---- tests/accuracy.py: the truth every working-precision check is measured against -----------------------------------------------
+def _stored(t, ref, n, rdt_in, definition=2.0 ** -57):
+    """|t - ref| elementwise against what `ref` can hold: `ref` is a value known to ~2^-60 rounded ONCE to float64 (half an ulp of each element,
+    2^-53 |ref|) plus the long-double summation error of the O(n^2) definition (sqrt(n) 2^-64 of the lane's rms per element, allowed as 2^-57 for
+    n <= 16384).  For f32 inputs truth() itself is a float64 FFT: its own error, at most log2(n) float64 epsilons of the lane's rms, is added."""
+    t = np.asarray(t); ref = np.asarray(ref)
+    rms = np.sqrt((np.abs(ref.astype(np.clongdouble)) ** 2).mean())
+    allow = 2.0 ** -53 * np.abs(ref) + definition * rms
+    if np.dtype(rdt_in) == np.float32:
+        allow = allow + np.log2(n) * 2.0 ** -52 * rms
+    d = np.abs(t.astype(np.clongdouble) - ref.astype(np.clongdouble))
+    return float((d / allow).max())
+
+
+@pytest.mark.parametrize("n,dt", BL_C2C)
+def test_truth_c2c_against_baseline_lengths(blvec, n, dt):
+    """accuracy.truth (long double through scipy.fft for f64 inputs, float64 for f32) against the committed long-double definition on lane 0 and the
+    mpmath bins, to the precision those are stored in (float64)."""
+    rdt = np.float64 if dt == "f64" else np.float32
+    key = f"c2c_{dt}_n{n}"; x = blvec[key + "_in"]
+    t = acc.truth("ndfft", x, n, 1)
+    assert t.dtype == (np.clongdouble if dt == "f64" else np.complex128)
+    assert _stored(t[0], blvec[key + "_fft_ld"], n, rdt) <= 1, "fft vs long-double definition"
+    assert _stored(t[0, blvec[key + "_mp_bins"]], blvec[key + "_fft_mp"], n, rdt) <= 1, "fft vs mpmath bins"
+    assert _stored(acc.truth("ndifft", x, n, 1)[0], blvec[key + "_ifft_ld"], n, rdt) <= 1, "ifft vs long-double definition"
+
+
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+def test_truth_real_against_baseline_lengths(blvec, dt):
+    n = 8192
+    rdt = np.float64 if dt == "f64" else np.float32
+    key = f"real_{dt}_n{n}"; xr, xh = blvec[key + "_r_in"], blvec[key + "_h_in"]
+    t = acc.truth("ndfft_r2c", xr, n, 1)
+    assert _stored(t[0], blvec[key + "_r2c_ld"], n, rdt) <= 1, "r2c vs long-double definition"
+    assert _stored(t[0, blvec[key + "_mp_bins"]], blvec[key + "_r2c_mp"], n, rdt) <= 1, "r2c vs mpmath bins"
+    assert _stored(acc.truth("ndifft_r2c", xh, n, 1)[0], blvec[key + "_c2r_ld"], n, rdt) <= 1, "c2r vs long-double definition (Im DC / Nyquist dropped)"
+
+
+def test_truth_dct_against_baseline_lengths(blvec):
+    """The committed DCT definitions take cosl of UNREDUCED long-double arguments up to pi n (tests/golden/make_golden_baseline.py: pi j k / (n - 1) and the
+    like, three roundings of 2^-64 each and pi's own): an angle error of up to 3.5 x 2^-64 x 512 pi = 2^-51.5 per term, which a sum of n terms of random
+    sign carries to sqrt(2) x that of the output's rms at worst.  So those lanes pin the truth to 2^-51 of the lane's rms, no better."""
+    x = blvec["dct_f64_n512_in"]
+    for k in (1, 2, 3, 4):
+        assert _stored(acc.truth(f"nddct{k}", x, 512, 1)[0], blvec[f"dct_f64_n512_dct{k}_ld"], 512, np.float64, definition=2.0 ** -51) <= 1, f"dct{k} vs long-double definition"
+
+
+def test_accuracy_metrics_and_inputs():
+    """errors(): a lane off by exactly one eps of its rms in one bin reads e_bin = 1, e_l2 = 1 / sqrt(n); a NaN reads nan (and so fails any bar).
+    make_input(): the impulse sits at (7 lane + 1) mod len of every lane whatever the axis; the graded input falls by 10^-6 along the lane."""
+    n = 64
+    ref = np.ones((3, n)); got = ref.copy(); got[1, 5] += np.finfo(np.float64).eps
+    e_l2, e_bin = acc.errors(got, ref, 1, np.float64)
+    assert abs(e_bin - 1) < 1e-12 and abs(e_l2 - 1 / np.sqrt(n)) < 1e-12
+    got[2, 0] = np.nan
+    assert all(e != e for e in acc.errors(got, ref, 1, np.float64))
+    x = acc.make_input("impulse", "ndfft", (3, 10, 4), 1, np.float32)
+    assert x.dtype == np.complex64 and x.sum() == 12
+    for lane, (i, k) in enumerate((i, k) for i in range(3) for k in range(4)):
+        assert x[i, (7 * lane + 1) % 10, k] == 1
+    g = acc.make_input("graded", "nddct2", (2, 1000), 1, np.float64); u = acc.make_input("uniform", "nddct2", (2, 1000), 1, np.float64)
+    assert np.allclose(g[:, 500], u[:, 500] * 1e-3, rtol=1e-12) and np.array_equal(g[:, 0], u[:, 0])
+    assert acc.kept_lanes(13).nonzero()[0].tolist() == [0, 5, 6, 10, 12]
 
 
 # ---- long-double definitions ------------------------------------------------------------------
