@@ -28,8 +28,10 @@ extern "C" {
 
 #define NDFFT_ABI_VERSION 1
 /* Minor revision: bumped when entry points are ADDED (existing ones keep their meaning).  1 = round-4 exports (ndfft_reload_switches,
- * ndfft_documented_switches, ndfft_set_input_hint ...); 2 = ndfft_abi_minor itself; 3 = ndfft_jit_prebuild (round 6). */
-#define NDFFT_ABI_MINOR 3
+ * ndfft_documented_switches, ndfft_set_input_hint ...); 2 = ndfft_abi_minor itself; 3 = ndfft_jit_prebuild (round 6); 4 = the entry
+ * points of ndfft_mi355x_ext.h (Normalization::Weights on device arrays).  Entry points added from minor 4 on are declared in
+ * ndfft_mi355x_ext.h, which includes this header. */
+#define NDFFT_ABI_MINOR 4
 
 typedef enum {
     NDFFT_OK = 0,
@@ -72,6 +74,8 @@ typedef enum {
  * Forward C2C and R2C ignore it (lib.rs:313-318, 497-503).  NDFFT_NORM_SCALE applies the caller's
  * scalar at that same point.  Normalization::Custom(fn) is a host function pointer and cannot
  * cross to the GPU: the language shim applies it on the host and calls with NONE.
+ * A DIAGONAL custom normalisation (one factor per element of the lane) has a device form of its own, Normalization::Weights:
+ * the vector of factors lives in device memory and is applied at the same points by the weighted call of ndfft_mi355x_ext.h.
  */
 typedef enum { NDFFT_NORM_NONE = 0, NDFFT_NORM_DEFAULT = 1, NDFFT_NORM_SCALE = 2 } ndfft_norm;
 

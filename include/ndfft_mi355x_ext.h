@@ -1,0 +1,45 @@
+/*
+ * ndfft_mi355x_ext.h -- entry points added to libndfft_mi355x.so after the core header was frozen for its C99 consumers
+ * (ABI minor 4).  C99; includes ndfft_mi355x.h.
+ *
+ * Normalization::Weights(w): a DIAGONAL normalisation -- a different factor per element of the lane (orthonormal DCT
+ * scalings, DCT-I end-point factors, spectral filters, de-aliasing masks).  Unlike Normalization::Custom(fn), a host
+ * function that can never run on the GPU, a diagonal is a vector, and the vector lives in device memory.
+ *
+ * The weights multiply the lane element by element at the point where the reference would call the custom function, and like
+ * Custom they REPLACE the default scaling (nothing is applied on top):
+ *
+ *   op                       where                                              weighted lane     d_weights
+ *   NDFFT_OP_C2C_FWD, R2C    ignored (lib.rs:313-318, 497-503)                  --                may be NULL
+ *   NDFFT_OP_C2C_INV         after, on the output lane (lib.rs:326-330)         n complex         n x Complex<T>
+ *   NDFFT_OP_C2R             before, on the input lane; then Im(DC) and, for    n/2 + 1 complex   (n/2 + 1) x Complex<T>
+ *                            even n, Im(Nyquist) are dropped (lib.rs:511-521)
+ *   NDFFT_OP_DCT1..4         before, on the input lane (lib.rs:692-696)         n real            n x T
+ *
+ * Complex weights on complex lanes: the full complex product.
+ */
+#ifndef NDFFT_MI355X_EXT_H
+#define NDFFT_MI355X_EXT_H
+
+#include "ndfft_mi355x.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ndfft_exec_device with Normalization::Weights.  Asynchronous on `stream`; the same argument checks, with the same panic texts in
+ * the same order, as ndfft_exec_device.  d_weights: device memory of the element type in the table above, read on `stream`;
+ * n_weights must equal the weighted lane's length (NDFFT_ERR_INVALID_ARG otherwise; the message names both numbers).  For the two
+ * forward ops the weights are ignored and may be NULL; for every other op a NULL d_weights is NDFFT_ERR_INVALID_ARG.
+ * C2R and DCT-I..IV weight the caller's input into a scratch image kept per host thread and stream (allocated by the first call of a
+ * size: warm a shape up before capturing it into a HIP graph, as for every multi-pass route); C2C inverse weights the output view in
+ * place, after the transform, and writes nothing outside it.  ndfft_last_path() reports "weights+<route>" / "<route>+weights". */
+int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in, void *d_out, int ndim,
+                               const int64_t *shape_in, const int64_t *stride_in,
+                               const int64_t *shape_out, const int64_t *stride_out,
+                               int axis, const void *d_weights, size_t n_weights, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* NDFFT_MI355X_EXT_H */

@@ -5,7 +5,7 @@
 //
 //   reference (src/lib.rs)                       here
 //   ------------------------------------------   ---------------------------------------------
-//   Normalization<T> {None, Default, Custom(fn)}  ndrustfft::Normalization<T>            (89-98)
+//   Normalization<T> {None, Default, Custom(fn)}  ndrustfft::Normalization<T>            (89-98)   + Weights(w): the diagonal form of Custom, applied on the device
 //   FftHandler<T>::new(n).normalization(..)       ndrustfft::FftHandler<T>(n).normalization(..) (269-311)
 //   R2cFftHandler<T>, DctHandler<T>               same names                              (451-495, 640-686)
 //   ndfft / ndifft / ndfft_r2c / ndifft_r2c /     same names, + _par twins                (350-421, 543-611,
@@ -17,6 +17,8 @@
 // Header-only; link with -lndfft_mi355x.  The GPU does all the arithmetic; there is no CPU path.
 #pragma once
 #include <complex>
+#include <memory>
+#include <mutex>
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
@@ -25,7 +27,7 @@
 #include <utility>
 #include <vector>
 
-#include "ndfft_mi355x.h"
+#include "ndfft_mi355x_ext.h"
 
 namespace ndrustfft {
 
@@ -53,12 +55,40 @@ template <> struct dtype_of<double> { static constexpr int value = NDFFT_F64; };
 }  // namespace detail
 
 // ---- Normalization<T> (lib.rs:89-98) -------------------------------------------------------------
+namespace detail {
+// the vector of a Normalization::weights: the host copy, and its device copy (uploaded once, on first use with a DeviceArray, to the
+// device that is current then; freed with the last Normalization that shares it).  ONE device per Normalization: the C ABI has no
+// "which device is current" query, so a Normalization that has been used on one GPU must not be used with DeviceArrays of another
+// (make one Normalization::weights per device).  The first use may come from any thread (the upload is serialised).
+template <typename T> struct WeightsBuf {
+    std::vector<T> host;
+    void *dev = nullptr;
+    std::mutex mu;
+    explicit WeightsBuf(std::vector<T> w) : host(std::move(w)) {}
+    WeightsBuf(const WeightsBuf &) = delete;
+    WeightsBuf &operator=(const WeightsBuf &) = delete;
+    ~WeightsBuf() { if (dev) ndfft_dev_free(dev); }
+    const void *device() {
+        std::lock_guard<std::mutex> lock(mu);
+        if (!dev && !host.empty()) {
+            check(ndfft_dev_alloc(&dev, host.size() * sizeof(T)));
+            check(ndfft_dev_upload(dev, host.data(), host.size() * sizeof(T)));
+        }
+        return dev;
+    }
+};
+}  // namespace detail
+
+// Weights(w) has no counterpart in the reference: it is the DIAGONAL form of Custom -- the lane is multiplied element by element by w where the
+// reference would call the custom function (and, like Custom, instead of the default scaling) -- and the only one of the two that runs on the GPU.
 template <typename T> struct Normalization {
-    enum Kind { None, Default, Custom } kind = Default;
+    enum Kind { None, Default, Custom, Weights } kind = Default;
     void (*fn)(T *data, std::size_t len) = nullptr;   // Custom(fn(&mut [T])): a plain function pointer
-    static Normalization none() { return {None, nullptr}; }
-    static Normalization dflt() { return {Default, nullptr}; }
-    static Normalization custom(void (*f)(T *, std::size_t)) { return {Custom, f}; }
+    std::shared_ptr<detail::WeightsBuf<T>> w;         // Weights(w)
+    static Normalization none() { return {None, nullptr, nullptr}; }
+    static Normalization dflt() { return {Default, nullptr, nullptr}; }
+    static Normalization custom(void (*f)(T *, std::size_t)) { return {Custom, f, nullptr}; }
+    static Normalization weights(std::vector<T> v) { return {Weights, nullptr, std::make_shared<detail::WeightsBuf<T>>(std::move(v))}; }
 };
 
 // ---- a minimal strided view (what the nd* functions need from ndarray's ArrayBase) -------------------
@@ -246,6 +276,25 @@ template <typename A> std::vector<std::int64_t> c_strides(const std::vector<std:
     return s;
 }
 
+// Normalization::weights on host arrays: every lane of the view along `axis` times w, element by element
+inline void check_weights_len(std::size_t got, std::int64_t want) {
+    if ((std::int64_t)got != want)
+        throw Error(NDFFT_ERR_INVALID_ARG, "weights: got " + std::to_string(got) + " expected " + std::to_string(want) + " (the length of the weighted lane)");
+}
+template <typename A> void weigh_lanes(A *ptr, const std::vector<std::int64_t> &shape, const std::vector<std::int64_t> &strides, std::size_t axis,
+                                       const std::vector<A> &w) {
+    check_weights_len(w.size(), shape[axis]);
+    std::size_t total = 1;
+    for (auto e : shape) total *= (std::size_t)e;
+    std::vector<std::int64_t> ix(shape.size(), 0);
+    for (std::size_t k = 0; k < total; ++k) {
+        std::int64_t off = 0;
+        for (std::size_t d = 0; d < ix.size(); ++d) off += ix[d] * strides[d];
+        ptr[off] *= w[(std::size_t)ix[axis]];
+        for (std::size_t d = ix.size(); d-- > 0;) { if (++ix[d] < shape[d]) break; ix[d] = 0; }
+    }
+}
+
 // NormT = element type the handler's Normalization acts on; pre = applied BEFORE the transform on the
 // input lane (C2R, DCT: lib.rs:511-515, 692-696) or AFTER on the output lane (C2C inverse: 326-330)
 template <typename In, typename Out, typename NormT>
@@ -257,12 +306,17 @@ void transform(int op, const ArrayView<const In> &input, ArrayView<Out> &output,
     if (norm.kind == Normalization<NormT>::None) mode = NDFFT_NORM_NONE;
     const bool custom = norm.kind == Normalization<NormT>::Custom && norm_applies;
     if (norm.kind == Normalization<NormT>::Custom) mode = NDFFT_NORM_NONE;
+    const bool weights = norm.kind == Normalization<NormT>::Weights && norm_applies;
+    if (norm.kind == Normalization<NormT>::Weights) mode = NDFFT_NORM_NONE;
     if (axis > 0x7fffffffu) throw Panic(NDFFT_ERR_AXIS, "index out of bounds");
-    if (custom && norm_is_pre) {
+    // (a vector of the wrong length is refused before anything runs, like on the device path: against the HANDLER's lane length, so that an array of the wrong size still gets the reference's panic from the C side)
+    if (weights) check_weights_len(norm.w->host.size(), (std::int64_t)(norm_is_pre ? ndfft_plan_lane_len_in(plan, op) : ndfft_plan_lane_len_out(plan, op)));
+    if ((custom || weights) && norm_is_pre) {
         if constexpr (std::is_same<In, NormT>::value) {
             if (axis < input.ndim()) {
                 std::vector<In> tmp = gather_c_order<In>(input);
-                for_each_lane<In>(tmp.data(), input.shape, axis, norm.fn);
+                if (weights) weigh_lanes<In>(tmp.data(), input.shape, c_strides<In>(input.shape), axis, norm.w->host);
+                else for_each_lane<In>(tmp.data(), input.shape, axis, norm.fn);
                 auto cs = c_strides<In>(input.shape);
                 check(exec_host(par, plan, op, tmp.data(), output.ptr, ndim, input.shape.data(), cs.data(), output.shape.data(),
                                 output.strides.data(), (int)axis, mode));
@@ -272,6 +326,9 @@ void transform(int op, const ArrayView<const In> &input, ArrayView<Out> &output,
     }
     check(exec_host(par, plan, op, input.ptr, output.ptr, ndim, input.shape.data(), input.strides.data(), output.shape.data(),
                     output.strides.data(), (int)axis, mode));
+    if (weights && !norm_is_pre) {
+        if constexpr (std::is_same<Out, NormT>::value) weigh_lanes<Out>(output.ptr, output.shape, output.strides, axis, norm.w->host);
+    }
     if (custom && !norm_is_pre) {
         if constexpr (std::is_same<Out, NormT>::value) {
             std::vector<Out> tmp = gather_c_order<Out>(ArrayView<const Out>{output.ptr, output.shape, output.strides});
@@ -292,7 +349,7 @@ void transform(int op, const ArrayView<const In> &input, ArrayView<Out> &output,
 // ---- device-resident arrays: keep `work` arrays in HBM between axis passes ----------
 // DeviceArray<A> owns a C-layout array in device memory.  The nd* overloads on DeviceArray go through
 // ndfft_exec_device (asynchronous on the default stream); upload()/download() are the only PCIe traffic.
-// Normalization::Custom is a host function: on this path it costs one round trip of the array it acts on.
+// Normalization::Custom is a host function: on this path it costs one round trip of the array it acts on.  Normalization::weights stays on the device.
 template <typename A> class DeviceArray {
   public:
     DeviceArray() = default;
@@ -353,6 +410,13 @@ void transform_device(int op, const DeviceArray<In> &input, DeviceArray<Out> &ou
     const bool custom = norm.kind == Normalization<NormT>::Custom && norm_applies;
     const int mode = norm.kind == Normalization<NormT>::Default ? NDFFT_NORM_DEFAULT : NDFFT_NORM_NONE;
     if (axis > 0x7fffffffu) throw Panic(NDFFT_ERR_AXIS, "index out of bounds");
+    if (norm.kind == Normalization<NormT>::Weights && norm_applies) {
+        // the diagonal pass runs on the device, asynchronously like the transform: no host copy.  (The sharded entry points take no weights: a _par
+        // call with weights runs on the current device alone.)
+        check(ndfft_exec_weighted_device(plan, op, input.ptr(), output.ptr(), (int)input.shape().size(), input.shape().data(), input.strides().data(),
+                                         output.shape().data(), output.strides().data(), (int)axis, norm.w->device(), norm.w->host.size(), nullptr));
+        return;
+    }
     const void *in_ptr = input.ptr();
     void *staged = nullptr;
     if (custom && norm_is_pre) {

@@ -27,6 +27,8 @@ SYMBOLS = [
     "ndfft_release_workspace", "ndfft_host_alloc", "ndfft_host_free", "ndfft_set_input_hint", "ndfft_host_forget", "ndfft_host_reg_cache", "ndfft_last_input_policy",
     "ndfft_documented_switches", "ndfft_reload_switches", "ndfft_jit_prebuild",
 ]
+# the entry points of include/ndfft_mi355x_ext.h (ABI minor 4 on): added after the core header was frozen for its C99 consumers
+EXT_SYMBOLS = ["ndfft_exec_weighted_device"]
 
 
 _loaded = []          # every Library this process has opened (tests/conftest.py reloads their switches between tests)
@@ -92,6 +94,11 @@ class Library:
         try:
             L.ndfft_jit_prebuild.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i32, i32, ip, ip, ip]; L.ndfft_jit_prebuild.restype = i32
         except AttributeError:      # a side build older than ABI minor 3 loaded through NDFFT_MI355X_LIB (A-B runs against earlier rounds); tests/test_abi.py checks the product's exports
+            if not os.environ.get("NDFFT_MI355X_LIB"):
+                raise
+        try:
+            L.ndfft_exec_weighted_device.argtypes = [vp, i32, vp, vp, i32, i64p, i64p, i64p, i64p, i32, vp, sz, vp]; L.ndfft_exec_weighted_device.restype = i32
+        except AttributeError:      # a side build older than ABI minor 4 (see above): Normalization.weights raises there
             if not os.environ.get("NDFFT_MI355X_LIB"):
                 raise
 

@@ -96,8 +96,28 @@ def _transform(op, inp, out, handler, axis, par=False):
     norm = handler.norm
     mode, scale = _lib.NORM_DEFAULT, 0.0
     post_custom = False
+    weights = post_weights = None
     if norm.kind == Normalization.NONE:
         mode = _lib.NORM_NONE
+    elif norm.kind == Normalization.WEIGHTS:
+        # the diagonal form of Custom: applied where Custom would be, replaces the default scaling.  Device tensors: the weighted entry point
+        # (no host copy, no synchronisation); numpy arrays: one vectorised multiply on the host around ndfft_exec
+        mode = _lib.NORM_NONE
+        if op not in (_lib.OP_C2C_FWD, _lib.OP_R2C):
+            post = op == _lib.OP_C2C_INV
+            side = out if post else inp
+            wlen = handler.n // 2 + 1 if op == _lib.OP_C2R else handler.n      # the weighted lane's length under this handler
+            wdt = handler.complex_dtype if (post or in_c) else handler.real_dtype
+            norm.host_weights(wdt, wlen)               # a vector of the wrong length: ValueError before anything runs
+            if axis < side.ndim and int(side.shape[axis]) == wlen:     # (else the C side raises the reference's index / size panic)
+                if dev:
+                    weights = norm.device_weights(wdt, wlen, out.device)
+                else:
+                    w = norm.host_weights(wdt, wlen).reshape([wlen if d == axis else 1 for d in range(side.ndim)])
+                    if post:
+                        post_weights = w
+                    else:
+                        inp = inp * w                  # a copy of the input, weighted (broadcast along every other dim)
     elif norm.kind == "Custom":
         mode = _lib.NORM_NONE
         if op in (_lib.OP_C2C_FWD, _lib.OP_R2C):
@@ -123,7 +143,12 @@ def _transform(op, inp, out, handler, axis, par=False):
         # the C side picks twiddle tables, JIT modules and workspaces by the CURRENT device: make it the tensors' one
         with torch.cuda.device(out.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-            if par and _PAR_DEVICES and len(_PAR_DEVICES) > 1:
+            if weights is not None:
+                # (the sharded entry points take no weights: a _par call with weights runs on the current device alone)
+                st = L.c.ndfft_exec_weighted_device(handler._plan, op, ctypes.c_void_p(inp.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                    inp.ndim, _i64(shape_in), _i64(sin), _i64(shape_out), _i64(sout), int(axis),
+                                                    ctypes.c_void_p(weights.data_ptr()), int(weights.shape[0]), stream)
+            elif par and _PAR_DEVICES and len(_PAR_DEVICES) > 1:
                 ids = (ctypes.c_int * len(_PAR_DEVICES))(*_PAR_DEVICES)
                 st = L.c.ndfft_exec_sharded_device(handler._plan, op, ctypes.c_void_p(inp.data_ptr()), ctypes.c_void_p(out.data_ptr()),
                                                    inp.ndim, _i64(shape_in), _i64(sin), _i64(shape_out), _i64(sout), int(axis), mode,
@@ -146,6 +171,8 @@ def _transform(op, inp, out, handler, axis, par=False):
             st = L.c.ndfft_exec(handler._plan, op, ctypes.c_void_p(inp.ctypes.data), ctypes.c_void_p(out.ctypes.data), inp.ndim,
                                 _i64(inp.shape), _i64(sin), _i64(out.shape), _i64(sout), int(axis), mode, scale)
     L.check(st)
+    if post_weights is not None:
+        out *= post_weights
     if post_custom:
         host = out.cpu().numpy() if dev else out
         lanes = np.moveaxis(host, axis, -1)

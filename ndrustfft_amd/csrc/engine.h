@@ -289,5 +289,10 @@ template <typename T> int launch_jit_real(int gen_op, const JitCfg &cfg, bool co
 // out[b][c][r] = in[b][r][c];  in pitch = ld_in elements per row, out pitch = ld_out
 int launch_transpose(const void *in, void *out, int64_t batch, int64_t rows, int64_t cols, int64_t ld_in,
                      int64_t ld_out, int64_t bstride_in, int64_t bstride_out, int elem_bytes, hipStream_t s);
+// transpose.hip (weights_kernel.h) : the diagonal normalisation pass, dst[lane, j] = src[lane, j] * w[j] over the lanes of gs / gd (same batch extents, n elements
+// per lane; real elements of `dtype`, or complex ones: the full complex product).  dst == src with identical geometry is legal.  nt_store: streaming stores
+// (a final result) instead of cache-allocating ones (an intermediate that is read again at once).
+int launch_weights(const void *src, void *dst, const void *w, const LaneGeom &gs, const LaneGeom &gd, int64_t n, int dtype, int cplx,
+                   int nt_store, hipStream_t s);
 
 }  // namespace ndfft

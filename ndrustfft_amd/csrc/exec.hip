@@ -15,6 +15,7 @@
 
 #include "exec_internal.h"
 #include "pow2_real.h"
+#include "../../include/ndfft_mi355x_ext.h"
 
 namespace ndfft {
 
@@ -1132,6 +1133,85 @@ int dispatch_peeled(Problem &P, const char *d_in, char *d_out, size_t ein, size_
     return NDFFT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Normalization::Weights (ndfft_exec_weighted_device): the diagonal pass of weights_kernel.h around dispatch(), at the reference's
+// application points.  The transform itself runs with scale 1 on the route it would take anyway.
+// ---------------------------------------------------------------------------------------------
+static void lane_geoms(const Problem &P, LaneGeom &gi, LaneGeom &go) {
+    gi.axis_stride = P.xs; go.axis_stride = P.ys; gi.nb = go.nb = (int32_t)P.b.size(); gi.pad_ = go.pad_ = 0;
+    for (size_t i = 0; i < P.b.size(); ++i) { gi.bshape[i] = go.bshape[i] = P.b[i].shape; gi.bstride[i] = P.b[i].sin; go.bstride[i] = P.b[i].sout; }
+}
+// a route followed by the weight pass: its path is "<route>+weights"
+static int suffixed(int rc, const char *suffix) {
+    if (rc == NDFFT_OK) {
+        static thread_local std::string path;
+        path = std::string(last_path()) + suffix;
+        set_last_path(path.c_str());
+    }
+    return rc;
+}
+// one problem of <= kMaxBatchDims batch dims
+static int weighted(const Problem &P, const char *d_in, char *d_out, const void *d_w, hipStream_t stream) {
+    const int dtype = P.plan->dtype;
+    int rc;
+    LaneGeom gi, go;
+    if (P.op == NDFFT_OP_C2C_INV) {
+        // after, on the output lane (lib.rs:326-330): in place on the output view, the final result -> streaming stores like the transform kernels' own
+        if ((rc = dispatch(P, d_in, d_out, stream))) return rc;
+        lane_geoms(P, gi, go);
+        return suffixed(launch_weights(d_out, d_out, d_w, go, go, P.ylen, dtype, 1, 1, stream), "+weights");
+    }
+    // before, on the input lane (lib.rs:511-515, 692-696): caller's input -> a dense image IN THE INPUT'S OWN DIMENSION ORDER (dims sorted by |stride| get dense
+    // positive strides; a broadcast BATCH dim keeps stride 0 and is not materialised), so that the transform takes the route it would take on the caller's array
+    const int cplx = op_in_cplx(P.op) ? 1 : 0;
+    const size_t ein = real_size(dtype) * (cplx ? 2 : 1);
+    Problem Q = P;
+    const int nd = (int)P.b.size() + 1;            // index nd - 1: the axis
+    int order[kMaxBatchDims + 1];
+    auto stride_of = [&](int i) { return i == nd - 1 ? P.xs : P.b[i].sin; };
+    auto shape_of = [&](int i) { return i == nd - 1 ? P.xlen : P.b[i].shape; };
+    for (int i = 0; i < nd; ++i) order[i] = i;
+    std::stable_sort(order, order + nd, [&](int a, int b) {
+        const int64_t sa = std::llabs(stride_of(a)), sb = std::llabs(stride_of(b));
+        return sa != sb ? sa < sb : a > b;           // equal strides (extent-1 lanes): the later dim is the faster one, as in C order
+    });
+    int64_t run = 1;
+    for (int k = 0; k < nd; ++k) {
+        const int i = order[k];
+        // (only a BATCH dim may stay broadcast: a diagonal does not commute with broadcasting along the lane, x * w[j] differs from j to j, so the axis is always materialised)
+        const int64_t st = i != nd - 1 && stride_of(i) == 0 ? 0 : run;
+        if (st) run *= shape_of(i);
+        if (i == nd - 1) Q.xs = st; else Q.b[i].sin = st;
+    }
+    void *S;
+    if ((rc = get_scratch(8, stream, (size_t)run * ein, &S))) return rc;
+    DeviceWs *ws;
+    if ((rc = current_ws(&ws))) return rc;
+    lane_geoms(P, gi, go);
+    LaneGeom gq, unused;
+    lane_geoms(Q, gq, unused);
+    // the image is read again at once by the transform: plain, cache-allocating stores
+    if ((rc = launch_weights(d_in, S, d_w, gi, gq, P.xlen, dtype, cplx, 0, stream))) return rc;
+    // Speed only: what the row kernels' load policy should expect of the image.  Noted BEFORE dispatch() on purpose, so that a route with a load policy sees the image as
+    // just written (small: resident, plain loads; above 64 MiB: streaming loads); that route's own row_load_policy then notes the read.  Routes without a policy leave the
+    // read un-noted.  Neither choice has been measured against the alternative.
+    ws->mall.note_write(S, (size_t)run * ein);
+    return prefixed("weights+", dispatch(Q, S, d_out, stream));
+}
+// more than kMaxBatchDims un-mergeable batch dims: peeled on the host like dispatch_peeled; every piece is weighted
+static int weighted_peeled(Problem &P, const char *d_in, char *d_out, size_t ein, size_t eout, const void *d_w, hipStream_t stream) {
+    if (P.b.size() <= (size_t)kMaxBatchDims) return weighted(P, d_in, d_out, d_w, stream);
+    BatchDim outer = P.b.front();
+    Problem Q = P;
+    Q.b.erase(Q.b.begin());
+    Q.nlanes = P.nlanes / outer.shape;
+    for (int64_t i = 0; i < outer.shape; ++i) {
+        int rc = weighted_peeled(Q, d_in + i * outer.sin * (int64_t)ein, d_out + i * outer.sout * (int64_t)eout, ein, eout, d_w, stream);
+        if (rc) return rc;
+    }
+    return NDFFT_OK;
+}
+
 }  // namespace ndfft
 
 using namespace ndfft;
@@ -1151,6 +1231,30 @@ int ndfft_exec_device(const ndfft_plan *plan, int op, const void *d_in, void *d_
     const size_t r = real_size(plan->dtype);
     return dispatch_peeled(P, (const char *)d_in, (char *)d_out, op_in_cplx(op) ? 2 * r : r, op_out_cplx(op) ? 2 * r : r,
                            (hipStream_t)stream);
+}
+
+int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in, void *d_out, int ndim,
+                               const int64_t *shape_in, const int64_t *stride_in, const int64_t *shape_out,
+                               const int64_t *stride_out, int axis, const void *d_weights, size_t n_weights, void *stream) {
+    clear_err();
+    g_last_policy = -1;
+    Problem P;
+    bool nothing;
+    int rc = prepare(plan, op, ndim, shape_in, stride_in, shape_out, stride_out, axis, NDFFT_NORM_NONE, 0.0, P, nothing);
+    if (rc || nothing) return rc;
+    if (!d_in || !d_out) return fail(NDFFT_ERR_INVALID_ARG, "null array pointer");
+    const size_t r = real_size(plan->dtype);
+    const size_t ein = op_in_cplx(op) ? 2 * r : r, eout = op_out_cplx(op) ? 2 * r : r;
+    if (op == NDFFT_OP_C2C_FWD || op == NDFFT_OP_R2C)   // the forward lane methods never look at the normalisation (lib.rs:313-318, 497-503)
+        return dispatch_peeled(P, (const char *)d_in, (char *)d_out, ein, eout, (hipStream_t)stream);
+    if (!d_weights) return fail(NDFFT_ERR_INVALID_ARG, "null weights pointer");
+    const int64_t want = op == NDFFT_OP_C2C_INV ? P.ylen : P.xlen;
+    if ((int64_t)n_weights != want) {
+        char m[128];
+        snprintf(m, sizeof m, "weights: got %zu expected %lld (the length of the weighted lane)", n_weights, (long long)want);
+        return fail(NDFFT_ERR_INVALID_ARG, m);
+    }
+    return weighted_peeled(P, (const char *)d_in, (char *)d_out, ein, eout, d_weights, (hipStream_t)stream);
 }
 
 int ndfft_last_input_policy(void) { return g_last_policy; }

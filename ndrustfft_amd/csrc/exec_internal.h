@@ -126,7 +126,7 @@ struct MallModel {
 };
 struct DeviceWs {
     MallModel mall;
-    std::map<hipStream_t, Scratch> scratch[8];
+    std::map<hipStream_t, Scratch> scratch[9];   // 0..7: the multi-pass routes; 8: the image a weight pass writes ahead of the transform (exec.hip: weighted)
     Staging stage_in, stage_out;
     PinnedBuf bounce_in[3], bounce_out[3];
     Pipe pipe;

@@ -5,6 +5,7 @@
 // kernels, and transposed back -- replacing the reference's per-lane x.to_vec() / y.assign()
 // strided copies (src/lib.rs:133-134), which touch one cache line per element.
 #include "engine.h"
+#include "weights_kernel.h"   // the other layout-moving pass of this unit: the diagonal normalisation (launch_weights)
 
 namespace ndfft {
 

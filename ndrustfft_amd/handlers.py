@@ -8,12 +8,17 @@ from . import _lib
 
 
 class Normalization:
-    """enum Normalization<T> { None, Default, Custom(fn(&mut [T])) }  (lib.rs:89-98)."""
+    """enum Normalization<T> { None, Default, Custom(fn(&mut [T])) }  (lib.rs:89-98), and Weights(w): the diagonal form of Custom, a vector
+    of per-element factors that is applied on the device (include/ndfft_mi355x_ext.h)."""
     NONE = "None"
     DEFAULT = "Default"
+    WEIGHTS = "Weights"
 
-    def __init__(self, kind, fn=None):
+    def __init__(self, kind, fn=None, w=None):
         self.kind, self.fn = kind, fn
+        self._w = w                # Weights: the vector as given (1-D numpy array)
+        self._host = {}            # element dtype -> the vector cast to it
+        self._dev = {}             # (element dtype, torch device) -> device copy
 
     @staticmethod
     def none():
@@ -27,6 +32,59 @@ class Normalization:
     def custom(fn):
         """fn(lane) mutates one 1-D numpy lane in place -- a host function, as in the reference."""
         return Normalization("Custom", fn)
+
+    @staticmethod
+    def weights(w):
+        """A diagonal normalisation: the lane is multiplied element by element by `w` (1-D numpy array or torch tensor) where the reference
+        would call a custom function -- after the transform for ndifft (n complex factors), before it for ndifft_r2c (n/2 + 1 complex factors)
+        and nddct1..4 (n real factors); ndfft and ndfft_r2c ignore it.  Like Custom it replaces the default scaling.  `w` is cast to the
+        handler's element type at first use; for device tensors its device copy is cached here, per device, and the call stays on the GPU."""
+        if hasattr(w, "detach"):
+            w = w.detach().cpu().numpy()
+        w = np.array(w, copy=True)
+        if w.ndim != 1:
+            raise ValueError("weights must be one-dimensional")
+        return Normalization(Normalization.WEIGHTS, w=w)
+
+    @staticmethod
+    def weights_from(fn, n, dtype):
+        """Normalization.weights for a custom function that is DIAGONAL (element-wise and linear): w = fn(ones).  Checked on a seeded random lane r:
+        fn(r) must equal w * r to 4 eps of each element, else ValueError("not an element-wise function")."""
+        dtype = np.dtype(dtype)
+        w = np.ones(n, dtype)
+        fn(w)
+        rng = np.random.default_rng(20240607)
+        r = rng.uniform(-1.0, 1.0, n)
+        if dtype.kind == "c":
+            r = r + 1j * rng.uniform(-1.0, 1.0, n)
+        r = r.astype(dtype)
+        got = r.copy()
+        fn(got)
+        want = w * r
+        eps = np.finfo(dtype).eps
+        if got.shape != want.shape or not np.all(np.abs(got - want) <= 4 * eps * np.abs(want)):
+            raise ValueError("not an element-wise function")
+        return Normalization.weights(w)
+
+    def host_weights(self, dtype, length):
+        """The vector in element type `dtype`; ValueError unless it has `length` entries."""
+        if self._w.shape[0] != length:
+            raise ValueError(f"weights: got {self._w.shape[0]} expected {length} (the length of the weighted lane)")
+        dtype = np.dtype(dtype)
+        if dtype not in self._host:
+            if dtype.kind != "c" and np.iscomplexobj(self._w):
+                raise TypeError("complex weights on a real lane")
+            self._host[dtype] = np.ascontiguousarray(self._w.astype(dtype))
+        return self._host[dtype]
+
+    def device_weights(self, dtype, length, device):
+        """The same as a torch tensor on `device` (uploaded once per element type and device)."""
+        import torch
+        w = self.host_weights(dtype, length)
+        key = (np.dtype(dtype), str(device))
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(w).to(device)
+        return self._dev[key]
 
 
 def _dtype_code(dtype):

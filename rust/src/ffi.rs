@@ -73,6 +73,13 @@ extern "C" {
         shape_in: *const i64, stride_in: *const i64, shape_out: *const i64, stride_out: *const i64,
         axis: c_int, norm: c_int, scale: c_double, stream: *mut c_void,
     ) -> c_int;
+    /// include/ndfft_mi355x_ext.h (ABI minor 4): the same call under `Normalization::Weights` -- `d_weights` is device memory of the weighted lane's
+    /// element type, `n_weights` its length; ignored (may be null) for the two forward ops
+    pub fn ndfft_exec_weighted_device(
+        plan: *const ndfft_plan, op: c_int, d_input: *const c_void, d_output: *mut c_void, ndim: c_int,
+        shape_in: *const i64, stride_in: *const i64, shape_out: *const i64, stride_out: *const i64,
+        axis: c_int, d_weights: *const c_void, n_weights: usize, stream: *mut c_void,
+    ) -> c_int;
     pub fn ndfft_dev_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn ndfft_dev_free(d_ptr: *mut c_void) -> c_int;
     pub fn ndfft_dev_upload(d_dst: *mut c_void, h_src: *const c_void, bytes: usize) -> c_int;

@@ -10,6 +10,9 @@
 //! * `T: FftNum + FloatConst` exactly as in the reference (src/lib.rs:111); `FftNum` is implemented for `f32` and
 //!   `f64`, the two types rustfft implements it for, so code that is generic over the reference's bounds compiles.
 //! * The `_par` twins spread one call over the GPUs named by [`set_par_devices`] (one GPU: same as the serial name).
+//! * `Normalization::Weights(w)` (no counterpart in ndrustfft) is the diagonal form of `Custom` and the only one of the two that
+//!   runs on the GPU: `device::*` calls go through `ndfft_exec_weighted_device` (include/ndfft_mi355x_ext.h).  Like the rest of this
+//!   crate it has not been compiled in this repository's build environment (no cargo / rustc there).
 //! * `Normalization::Custom(f)` runs `f` on the host, on a lane-major copy, at the point the
 //!   reference applies it (after the inverse C2C transform; before the C2R and DCT transforms).
 //! * Errors of the device runtime panic with the HIP error string.
@@ -64,6 +67,38 @@ pub enum Normalization<T> {
     Default,
     /// A host function applied to every lane at the handler-specific point.
     Custom(fn(&mut [T])),
+    /// The DIAGONAL form of `Custom` (no counterpart in ndrustfft): the lane is multiplied element by element by the vector, at the
+    /// same point and, like `Custom`, instead of the default scaling.  On `device::DeviceArray`s it runs on the GPU
+    /// (`ndfft_exec_weighted_device`); on host arrays it is one multiply around `ndfft_exec`.
+    Weights(Weights<T>),
+}
+
+/// The vector of a `Normalization::Weights`: the host copy and, once a device call has used it, its device copy (shared by clones,
+/// freed with the last one).
+#[derive(Clone)]
+pub struct Weights<T>(std::sync::Arc<WeightsBuf<T>>);
+struct WeightsBuf<T> {
+    host: Vec<T>,
+    dev: std::sync::OnceLock<usize>, // device address of the uploaded copy
+}
+impl<T: Copy> Weights<T> {
+    /// One factor per element of the weighted lane: `n` for `ndifft` and `nddct1..4`, `n/2 + 1` for `ndifft_r2c`.
+    pub fn new(w: Vec<T>) -> Self { Weights(std::sync::Arc::new(WeightsBuf { host: w, dev: std::sync::OnceLock::new() })) }
+    pub fn as_slice(&self) -> &[T] { &self.0.host }
+    fn device_ptr(&self) -> *const c_void {
+        *self.0.dev.get_or_init(|| {
+            let mut p = std::ptr::null_mut();
+            let bytes = self.0.host.len().max(1) * std::mem::size_of::<T>();
+            check(unsafe { ffi::ndfft_dev_alloc(&mut p, bytes) });
+            check(unsafe { ffi::ndfft_dev_upload(p, self.0.host.as_ptr() as *const c_void, self.0.host.len() * std::mem::size_of::<T>()) });
+            p as usize
+        }) as *const c_void
+    }
+}
+impl<T> Drop for WeightsBuf<T> {
+    fn drop(&mut self) {
+        if let Some(&p) = self.dev.get() { unsafe { ffi::ndfft_dev_free(p as *mut c_void) }; }
+    }
 }
 
 struct Plan(*mut ffi::ndfft_plan);
@@ -145,6 +180,14 @@ fn apply_custom<A: Clone, S: DataMut<Elem = A>, D: Dimension>(arr: &mut ArrayBas
     }
 }
 
+/// Applies a Weights normalization: every lane along `axis` times `w`, element by element (host side).
+fn apply_weights<A: Copy + std::ops::Mul<Output = A>, S: DataMut<Elem = A>, D: Dimension>(arr: &mut ArrayBase<S, D>, axis: usize, w: &[A]) {
+    assert_eq!(arr.shape()[axis], w.len(), "weights: got {} expected {} (the length of the weighted lane)", w.len(), arr.shape()[axis]);
+    for mut lane in arr.lanes_mut(Axis(axis)) {
+        for (x, &f) in lane.iter_mut().zip(w) { *x = *x * f; }
+    }
+}
+
 /// bad axis: the reference indexes `output.shape()[axis]` first (src/lib.rs:116) and panics with this text
 fn check_axis(ndim: usize, axis: usize) {
     if axis >= ndim {
@@ -190,6 +233,9 @@ macro_rules! transform_body {
         if let Normalization::Custom(f) = $handler.norm {
             apply_custom($output, $axis, f);
         }
+        if let Normalization::Weights(ref w) = $handler.norm {
+            apply_weights($output, $axis, w.as_slice());
+        }
     }};
     (before, $input:ident, $output:ident, $handler:ident, $axis:ident, $op:expr, $par:expr) => {{
         check_axis($output.ndim(), $axis);
@@ -198,6 +244,12 @@ macro_rules! transform_body {
             // acts on the input: run on an owned copy so that `input` stays untouched (it is a shared borrow)
             let mut staged = $input.to_owned();
             apply_custom(&mut staged, $axis, f);
+            let (shape_in, stride_in) = strides_i64(&staged);
+            exec(&$handler.plan, $op, staged.as_ptr() as *const c_void, $output.as_mut_ptr() as *mut c_void, &shape_in, &stride_in,
+                 &shape_out, &stride_out, $axis, ffi::NDFFT_NORM_NONE, $par);
+        } else if let Normalization::Weights(ref w) = $handler.norm {
+            let mut staged = $input.to_owned();
+            apply_weights(&mut staged, $axis, w.as_slice());
             let (shape_in, stride_in) = strides_i64(&staged);
             exec(&$handler.plan, $op, staged.as_ptr() as *const c_void, $output.as_mut_ptr() as *mut c_void, &shape_in, &stride_in,
                  &shape_out, &stride_out, $axis, ffi::NDFFT_NORM_NONE, $par);
@@ -326,6 +378,17 @@ pub mod device {
         });
     }
 
+    /// `Normalization::Weights` on device arrays: the diagonal pass runs on the GPU around the transform, asynchronously, no host copy.
+    fn exec_weighted_device<T: FftNum + FloatConst, A, B, W: Copy>(plan: &Plan, op: c_int, input: &DeviceArray<A>, output: &mut DeviceArray<B>, axis: usize, w: &Weights<W>)
+    where A: Copy, B: Copy {
+        let (si, sti) = input.geom();
+        let (so, sto) = output.geom();
+        check(unsafe {
+            ffi::ndfft_exec_weighted_device(plan.0, op, input.ptr, output.ptr, si.len() as c_int, si.as_ptr(), sti.as_ptr(),
+                                            so.as_ptr(), sto.as_ptr(), axis as c_int, w.device_ptr(), w.as_slice().len(), std::ptr::null_mut())
+        });
+    }
+
     // the same three application points as the host functions (`transform_body!`): ignored / after / before
     macro_rules! device_transform {
         ($name:ident, $a:ty, $b:ty, $h:ident, $op:expr, ignored) => {
@@ -341,6 +404,9 @@ pub mod device {
             /// lanes after the transform (src/lib.rs:326-330): one extra round trip of the output array.
             pub fn $name<T: FftNum + FloatConst>(input: &DeviceArray<$a>, output: &mut DeviceArray<$b>, handler: &$h<T>, axis: usize) {
                 check_axis(output.shape.len(), axis);
+                if let Normalization::Weights(ref w) = handler.norm {
+                    return exec_weighted_device::<T, $a, $b, $b>(&handler.plan, $op, input, output, axis, w);
+                }
                 let mode = match handler.norm { Normalization::Default => ffi::NDFFT_NORM_DEFAULT, _ => ffi::NDFFT_NORM_NONE };
                 exec_device::<T, $a, $b>(&handler.plan, $op, input, output, axis, mode);
                 if let Normalization::Custom(f) = handler.norm {
@@ -354,6 +420,9 @@ pub mod device {
             /// INPUT lanes before the transform (src/lib.rs:511-515, 692-696): one extra round trip of the input array.
             pub fn $name<T: FftNum + FloatConst>(input: &DeviceArray<$a>, output: &mut DeviceArray<$b>, handler: &$h<T>, axis: usize) {
                 check_axis(output.shape.len(), axis);
+                if let Normalization::Weights(ref w) = handler.norm {
+                    return exec_weighted_device::<T, $a, $b, $a>(&handler.plan, $op, input, output, axis, w);
+                }
                 if let Normalization::Custom(f) = handler.norm {
                     let staged = input.map_lanes_on_host(axis, f);
                     exec_device::<T, $a, $b>(&handler.plan, $op, &staged, output, axis, ffi::NDFFT_NORM_NONE);
