@@ -225,65 +225,88 @@ template <typename T> int pow2_real_col_lanes(int F, int kind);   // adjacent la
 template <typename T> int pow2_real_narrow_lanes(int F);   // lanes per XCD-aware narrow column tile (0: none)
 void pow2_real_build_narrow_twiddles(int dtype, int F, HostTable &out);
 template <typename T> int launch_pow2_real_narrow(int gen_op, const RealArgs<T> &a, hipStream_t s);
-// column four-step, twiddled stage (kernels_colsplit.hip): cs = 1 C2C, 2 = R2C second stage, 3 = C2R first stage
-bool pow2_real_config(int F, JitCfg &cfg);
-template <typename T> int launch_jit_blue(int gen_op, const JitCfg &cfgM, bool col, const RealArgs<T> &a, hipStream_t s);
-// rader_kernel.h (jit.hip): recipe for an inner FFT length F with one prime factor > 13 (false: none, Bluestein stays), lanes per column tile, launch
-// Bluestein (jit.hip): convolution length for inner FFT length F -- the cheapest 13-smooth M in [2F - 1, m_pow2] by passes x M -- and the register recipe for it
-int blue_pick_len(int dtype, int F, int m_pow2);
-bool blue_plan_cfg(int dtype, int M, JitCfg &cfg);
-bool rader_choose(int dtype, int F, RaderCfg &rc, bool dct1_slot = false);
-template <typename T> int launch_jit_plain(int gen_op, const JitCfg &cfg, bool col, const RealArgs<T> &a, hipStream_t s);   // plain_kernel.h: odd-n real ops, smooth F
-bool jit_choose_real(int dtype, int F, JitCfg &cfg);   // jit_choose for the real-op slots (rows of RealPow2Kernel): cost-model recipe
-int rader_col_lanes(int dtype, const RaderCfg &rc);
-template <typename T> int launch_jit_rader(int gen_op, const RaderCfg &rc, bool col, const RealArgs<T> &a, hipStream_t s);
-int launch_pack_lanes(const void *strided, void *dense, const LaneGeom &g, int64_t lanes, int64_t len, int64_t pitch, int esz, int unpack, hipStream_t s);   // big.hip
+bool pow2_real_config(int F, JitCfg &cfg);   // the ahead-of-time recipe of length F as a JitCfg (false: none)
+
+// kernels_colsplit.hip : the twiddled stage of the column four-step (exec.hip: col_split); the values are RealPow2Kernel's CS parameter
+enum CsStage : int {
+    CS_C2C = 1,      // C2C, second stage: twiddle on load, rows k1 + F1 k2
+    CS_R2C_2 = 2,    // R2C, second stage: the same through the Hermitian row map
+    CS_C2R_1 = 3,    // C2R, first stage: Hermitian gather, inverse FFT, conjugate twiddle
+};
 int colsplit_inner_len();
 int colsplit_tile_lanes();
-template <typename T> int launch_colsplit(int cs, bool inverse, const RealArgs<T> &a, hipStream_t s);
+template <typename T> int launch_colsplit(CsStage stage, bool inverse, const RealArgs<T> &a, hipStream_t s);
 
-// kernels_fourstep.hip : the two passes of the row four-step on the column kernels (no transpose launch)
-bool jit_fourstep_choose(int dtype, int n, JitCfg &cfg);        // plan time: the recipe of those passes for a smooth non-power-of-two factor n (false: none)
-bool jit_fourstep_ok(int dtype, const JitCfg &cfg);
-bool jit_rfs1_ok(int dtype, const JitCfg &cfg);
-bool jit_rfsi_ok(int dtype, const JitCfg &cfg);                 // ... and the inverse direction's first pass (col_direct.h modes 7 / 8; whole butterfly rounds only)                 // the real four-step's first pass (real FFT of length 2 cfg.n over the strided index) can be specialised with hiprtc             // a smooth non-power-of-two factor whose four-step passes can be specialised with hiprtc (jit.hip)
-template <typename T> int launch_jit_fourstep(int pass, bool inverse, const JitCfg &cfg, const RealArgs<T> &a, hipStream_t s);
+// The passes of the row four-steps (exec.hip: big_fft, real_fourstep, real_fourstep_inv, dct4_fourstep).  Every pass has a form compiled ahead of time for the
+// factors 64..1024 (kernels_fourstep.hip, kernels_fourstep_real.hip) and one specialised with hiprtc for a smooth factor (jit.hip: launch_jit_fourstep).
+enum FsPass : int {
+    FS_CPX_1,        // complex pass 1: column load, row store -- also the fused DCT-IV first pass (RealArgs::makhoul = 2)
+    FS_CPX_2,        // complex pass 2: twiddle on load, column store
+    FS_REAL_1,       // real pass 1: R2C over the strided index, row store; F = N1 / 2
+    FS_HALF_2,       // real pass 2 writing the half spectrum -- also DCT-I (RealArgs::makhoul = 3)
+    FS_DCT2_2,       // real pass 2 writing DCT-II outputs
+    FS_C2R_1,        // inverse pass 1, C2R: Hermitian gather, inverse FFT, row store
+    FS_DCT3_1,       // inverse pass 1, DCT-III: the same with the pre-twiddle built on load
+    FS_DCT4_2,       // second pass of the fused DCT-IV four-step
+    FS_C2R_LAST,     // last pass of the inverse direction: column C2R on tiles of 128-byte rows; F = N1 / 2
+};
+// kernels_fourstep.hip : FS_CPX_1 / FS_CPX_2 for a factor F
 bool fourstep_supported(int F);
 void fourstep_build_wide_twiddles(int F, HostTable &out);       // empty unless F has a wide (E = 16) recipe
-bool fourstep_wide(int dtype, int pass, int F);                 // this pass of length F runs the wide recipe (the caller then passes twp_col_w and RealArgs::wide = 1)
-template <typename T> int launch_fourstep(int pass, int F, bool inverse, const RealArgs<T> &a, hipStream_t s);
-// kernels_fourstep_real.hip : the passes of the REAL four-step (stage: 1 = real column FFT, row store; 2 = twiddled column pass
-// writing the half spectrum (R2C) ; 3 = the same writing DCT-II outputs ; 4 / 5 = first pass of the inverse direction, C2R / DCT-III ; 6 = second pass of the fused DCT-IV four-step ; 7 = last pass of the inverse direction, column C2R)
+bool fourstep_wide(int dtype, FsPass pass, int F);              // FS_CPX_1 / FS_CPX_2 of length F runs the wide recipe (the caller then passes twp_col_w and RealArgs::wide = 1)
+template <typename T> int launch_fourstep(FsPass pass, int F, bool inverse, const RealArgs<T> &a, hipStream_t s);
+// kernels_fourstep_real.hip : the other seven passes (FS_REAL_1, FS_C2R_LAST: F = N1 / 2; the rest: F = N2)
 bool fourstep_real_supported(int N1, int N2);
-template <typename T> int launch_fourstep_real(int stage, int F, const RealArgs<T> &a, hipStream_t s);
+template <typename T> int launch_fourstep_real(FsPass pass, int F, const RealArgs<T> &a, hipStream_t s);
 
 // big.hip : four-step pieces for lanes that do not fit LDS
+int launch_pack_lanes(const void *strided, void *dense, const LaneGeom &g, int64_t lanes, int64_t len, int64_t pitch, int esz, int unpack, hipStream_t s);
 template <typename T>
 int launch_big_twiddle(cpx<T> *data, int64_t lanes, int F1, int F2, const cpx<T> *twlo, const cpx<T> *twhi, int logB, int conj,
                        T scale, hipStream_t s);
 template <typename T>
 int launch_blue_stage(int stage, cpx<T> *dst, int64_t pitch_dst, const cpx<T> *src, int64_t pitch_src, int64_t lanes, int F, int M,
-                      const cpx<T> *chirp, const cpx<T> *bhat, int inverse, T scale, hipStream_t s);   // 0 pre, 1 mid, 2 post (big.hip)
+                      const cpx<T> *chirp, const cpx<T> *bhat, int inverse, T scale, hipStream_t s);   // 0 pre, 1 mid, 2 post
 template <typename T>
 int launch_big_pre(int gen_op, const RealArgs<T> &a, cpx<T> *z, hipStream_t s, int conj_z = 0);    // raw lanes (a.in, a.pitch_in) -> z[lane][F] (conj_z: its conjugate)
 template <typename T>
 int launch_big_post(int gen_op, const RealArgs<T> &a, const cpx<T> *z, hipStream_t s);   // z[lane][F] -> a.out
-size_t generic_max_len(size_t csize);   // longest complex FFT the single-launch LDS kernel can hold
+size_t generic_max_len(size_t csize);   // (kernels_generic.hip) longest complex FFT the single-launch LDS kernel can hold
 
-// jit.hip : hiprtc specialisation of the register-resident kernel for smooth non-power-of-two lengths
-bool jit_choose(int dtype, int n, JitCfg &cfg, bool allow_partial = false);
-void shard_release_all();   // shard.hip: every shard worker frees its chunk buffers (ndfft_release_workspace)
+// shard.hip
+void shard_release_all();   // every shard worker frees its chunk buffers (ndfft_release_workspace)
+
+// jit.hip : the kernel headers specialised with hiprtc for one length and recipe.  A launcher returns NDFFT_ERR_UNSUPPORTED where no such kernel can be had.
+// -- recipes (plan time)
+bool jit_choose(int dtype, int n, JitCfg &cfg, bool allow_partial = false);   // register recipe of a smooth non-power-of-two length (false: none)
 bool jit_choose_col(int dtype, int n, const JitCfg &row_cfg, JitCfg &col_cfg);   // true: column tiles of a C2C plan should use col_cfg instead of row_cfg
-void jit_build_twiddles(const JitCfg &cfg, HostTable &out);
-int launch_jit_c2c(int dtype, const JitCfg &cfg, int nt, const Pow2Args &a, hipStream_t s);
-bool jit_c2c_row_vec(int dtype, JitCfg &cfg);   // f32 C2C rows: true = cfg was changed to the same radix list on half the threads (twice the elements), which can use 16-byte accesses (jit.hip)
-int jit_col_lanes(int dtype, const JitCfg &cfg, bool c2c = false);   // c2c: a 4-lane tile is acceptable (complex output rows)
-// thread-per-lane two-factor kernels (reg_kernel.h), specialised with hiprtc
-bool regfft_factor(int n, int *n1, int *n2);
-int regfft_max_n(int dtype);
-int launch_jit_regfft(int dtype, int n1, int n2, bool stage, const TinyArgs &a, hipStream_t s);
-int launch_jit_regreal(int dtype, int gop, int n, int f1, int f2, bool stage, const RegRealArgs &a, hipStream_t s);
-template <typename T> int launch_jit_real(int gen_op, const JitCfg &cfg, bool col, const RealArgs<T> &a, hipStream_t s);
+bool jit_choose_real(int dtype, int F, JitCfg &cfg);            // jit_choose for the real-op slots (rows of RealPow2Kernel): cost-model recipe
+bool jit_c2c_row_vec(int dtype, JitCfg &cfg);                   // f32 C2C rows: true = cfg was changed to the same radix list on half the threads, which can use 16-byte accesses
+bool jit_fourstep_choose(int dtype, int n, JitCfg &cfg);        // the recipe of the four-step passes for a smooth non-power-of-two factor n (false: none)
+void jit_build_twiddles(const JitCfg &cfg, HostTable &out);     // per-pass twiddles of a recipe
+int blue_pick_len(int dtype, int F, int m_pow2);                // Bluestein: convolution length for inner FFT length F -- the cheapest 13-smooth M in [2F - 1, m_pow2]
+bool blue_plan_cfg(int dtype, int M, JitCfg &cfg);              // ... and the register recipe for it
+bool rader_choose(int dtype, int F, RaderCfg &rc, bool dct1_slot = false);   // recipe for an inner FFT length F with one prime factor > 13 (false: none, Bluestein stays)
+bool regfft_factor(int n, int *n1, int *n2);                    // thread-per-lane kernels (reg_kernel.h): n = n1 * n2, both with a butterfly of their own
+int regfft_max_n(int dtype);                                    // ... and the longest lane they take
+// -- what hiprtc can build for a four-step pass: FS_CPX_1 / FS_CPX_2 / FS_HALF_2 / FS_DCT2_2, FS_REAL_1 (the rows' recipe), FS_C2R_1 / FS_DCT3_1 / FS_DCT4_2 (whole rounds only)
+bool jit_fourstep_ok(int dtype, const JitCfg &cfg);
+bool jit_rfs1_ok(int dtype, const JitCfg &cfg);
+bool jit_rfsi_ok(int dtype, const JitCfg &cfg);
+int jit_col_lanes(int dtype, const JitCfg &cfg, bool c2c = false);   // lanes per column tile (0: none); c2c: a 4-lane tile is acceptable (complex output rows)
+int rader_col_lanes(int dtype, const RaderCfg &rc);             // ... of the Rader kernel
+// -- launchers
+int launch_jit_c2c(int dtype, const JitCfg &cfg, int nt, const Pow2Args &a, hipStream_t s);                                  // pow2_kernel.h: C2C rows
+int launch_jit_regfft(int dtype, int n1, int n2, bool stage, const TinyArgs &a, hipStream_t s);                              // reg_kernel.h: C2C, one thread per lane
+int launch_jit_regreal(int dtype, int gop, int n, int f1, int f2, bool stage, const RegRealArgs &a, hipStream_t s);          // reg_kernel.h: the real-data ops, one thread per lane
+template <typename T> int launch_jit_real(int gen_op, const JitCfg &cfg, bool col, const RealArgs<T> &a, hipStream_t s);     // pow2_real.h: real-op rows, every op on column tiles
+template <typename T> int launch_jit_plain(int gen_op, const JitCfg &cfg, bool col, const RealArgs<T> &a, hipStream_t s);    // plain_kernel.h: odd-n real ops, smooth F
+template <typename T> int launch_jit_blue(int gen_op, const JitCfg &cfgM, bool col, const RealArgs<T> &a, hipStream_t s);    // blue_kernel.h: Bluestein on convolution length cfgM.n
+template <typename T> int launch_jit_rader(int gen_op, const RaderCfg &rc, bool col, const RealArgs<T> &a, hipStream_t s);   // rader_kernel.h
+// pow2_real.h / col_direct.h: a four-step pass.  `pass` is an FsPass, and exec.hip: fs_launch, the one caller, passes one.  The linked signature keeps its int:
+// a build of this library without hiprtc supplies the symbol from a stub of its own, and the stub of the commit before the enum has to link against this
+// library too (that commit's CPU tests are run against every later library).
+template <typename T> int launch_jit_fourstep(int pass, bool inverse, const JitCfg &cfg, const RealArgs<T> &a, hipStream_t s);
 
 // transpose.hip : batched LDS-padded 2-D transpose, elem size 4/8/16 bytes
 // out[b][c][r] = in[b][r][c];  in pitch = ld_in elements per row, out pitch = ld_out

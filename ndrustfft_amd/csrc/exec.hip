@@ -311,15 +311,58 @@ static bool plain_enabled() { return sw().plain; }                         // ND
 static bool blue_enabled() { return sw().blue; }                           // NDFFT_BLUE=0: Bluestein lengths on the LDS kernel
 static bool colsplit_enabled() { return sw().colsplit; }                   // NDFFT_COLSPLIT=0: long strided lanes on the narrow-tile / transpose routes
 
-// How one four-step pass of length F runs: on the kernel compiled ahead of time for F (`tables`: the sub-plan has its twiddles), on one
-// specialised with hiprtc (`recipe`: the sub-plan has one, `rtc_ok`: hiprtc can build that kernel), or not at all.
-enum FsPass { FS_NONE = 0, FS_AOT, FS_RTC };
-static FsPass fs_pass(int F, bool tables, bool recipe, bool (*rtc_ok)(int, const JitCfg &), int dtype, const JitCfg &cfg) {
-    if (fourstep_supported(F) && tables) return FS_AOT;
-    return recipe && rtc_ok(dtype, cfg) ? FS_RTC : FS_NONE;
-}
-static bool jit_col_ok(int dtype, const JitCfg &cfg) { return jit_col_lanes(dtype, cfg, false) > 0; }
 template <typename T> static int dtype_of() { return sizeof(T) == 8 ? NDFFT_F64 : NDFFT_F32; }
+
+// How one four-step pass (engine.h: FsPass) of length F runs, given the C2C or R2C sub-plan of that length: on the kernel compiled ahead of time for F, on one
+// specialised with hiprtc from the sub-plan's recipe, or not at all -- and with which of the sub-plan's per-pass twiddle tables.
+enum FsHow { FS_NONE = 0, FS_AOT, FS_RTC };
+struct FsPlan {
+    FsPass pass = FS_CPX_1; int F = 0; const ndfft_plan *sub = nullptr;
+    FsHow how = FS_NONE;
+    const JitCfg *recipe = nullptr;            // FS_RTC
+    void *DevConfig::*twp = nullptr;           // the twiddle table of that form ...
+    bool wide = false;                         // ... unless the pass runs the wide (E = 16) recipe on twp_col_w (kernels_fourstep.hip)
+    explicit operator bool() const { return how != FS_NONE; }
+};
+static bool jit_col_ok(int dtype, const JitCfg &cfg) { return jit_col_lanes(dtype, cfg, false) > 0; }
+static FsPlan fs_plan(FsPass pass, int F, const ndfft_plan *sub, int dtype) {
+    const FftConfig &c = sub->cfg[CFG_MAIN];
+    // What follows from the pass.  `rows`: an R2C sub-plan, the pass runs its rows' recipe and tables (a C2C sub-plan keeps separate ones for the four-step passes).
+    // `tables`: the ahead-of-time form needs the sub-plan's column twiddles -- checked on the complex routes, a given on the real ones.
+    // `rtc_ok`: hiprtc can build the kernel of this pass for the recipe.
+    bool rows = false, tables = true;
+    bool (*rtc_ok)(int, const JitCfg &) = jit_fourstep_ok;
+    switch (pass) {
+        case FS_CPX_1: case FS_CPX_2: tables = !c.twp_col.re.empty(); break;
+        case FS_DCT4_2: tables = !c.twp_col.re.empty(); rtc_ok = jit_rfsi_ok; break;
+        case FS_HALF_2: case FS_DCT2_2: break;
+        case FS_C2R_1: case FS_DCT3_1: rtc_ok = jit_rfsi_ok; break;
+        case FS_REAL_1: rows = true; rtc_ok = jit_rfs1_ok; break;
+        case FS_C2R_LAST: rows = true; rtc_ok = jit_col_ok; break;
+    }
+    const JitCfg &recipe = rows ? c.jitcfg : c.fs_jitcfg;
+    FsPlan p;
+    p.pass = pass; p.F = F; p.sub = sub;
+    if (fourstep_supported(F) && tables) {
+        p.how = FS_AOT; p.twp = rows ? &DevConfig::twp : &DevConfig::twp_col;
+        p.wide = (pass == FS_CPX_1 || pass == FS_CPX_2) && fourstep_wide(dtype, pass, F) && !c.twp_col_w.re.empty();
+    } else if ((rows ? c.jit : c.fs_jit) && rtc_ok(dtype, recipe)) {
+        p.how = FS_RTC; p.recipe = &recipe; p.twp = rows ? &DevConfig::twp : &DevConfig::twp_fs;
+    }
+    return p;
+}
+// Launches a planned pass on `a`, whose twiddle table (and wide flag) it sets.  kDeclined where the hiprtc launcher says unsupported.
+template <typename T>
+static int fs_launch(const FsPlan &p, bool inverse, RealArgs<T> &a, hipStream_t stream) {
+    const DevTables *dt;
+    const int rc = get_dev_tables(p.sub, &dt);
+    if (rc) return rc;
+    const DevConfig &d = dt->cfg[CFG_MAIN];
+    a.wide = p.wide && !a.makhoul ? 1 : 0;      // (the fused DCT-IV first pass, makhoul = 2, exists in the staged E = 8 form only: launch_fourstep)
+    a.twp = (const cpx<T> *)(a.wide ? d.twp_col_w : d.*p.twp);
+    if (p.how == FS_RTC) return jit_rc(launch_jit_fourstep<T>(p.pass, inverse, *p.recipe, a, stream));
+    return p.pass == FS_CPX_1 || p.pass == FS_CPX_2 ? launch_fourstep<T>(p.pass, p.F, inverse, a, stream) : launch_fourstep_real<T>(p.pass, p.F, a, stream);
+}
 
 // RealArgs of a four-step pass: zeroed (the struct's own defaults kept) but for the twiddles W_N^m = twhi[m >> logB] * twlo[m & (2^logB - 1)],
 // N = cs_n, and the lane split (o, k1) = divmod(L / inner, k1n) of pow2_real.h's CS kernels
@@ -334,9 +377,9 @@ static RealArgs<T> fs_args(const void *twlo, const void *twhi, int logB, int k1n
 // Column four-step (pow2_real.h, CS kernels): a long STRIDED power-of-two lane, n = F1 * F2, as two passes
 // of wide column tiles over a dense C-layout block [O][n][I] -- no transpose, no narrow tiles:
 //   C2C      A: column C2C of length F1 over a = row / F2 (lanes (b, i): F2*I contiguous)  -> S[o][k1][b][i]
-//            B: CS=1 kernel of length F2 over b, twiddle on load, rows k1 + F1 k2            -> out
-//   R2C      A: column R2C of length F1 (k1 = 0..F1/2); B: CS=2 kernel (Hermitian row map)   -> out rows 0..n/2
-//   C2R      A: CS=3 kernel (Hermitian gather, inverse F2, conj twiddle) -> S; B: column C2R of length F1 -> out
+//            B: CS_C2C kernel of length F2 over b, twiddle on load, rows k1 + F1 k2            -> out
+//   R2C      A: column R2C of length F1 (k1 = 0..F1/2); B: CS_R2C_2 kernel (Hermitian row map)   -> out rows 0..n/2
+//   C2R      A: CS_C2R_1 kernel (Hermitian gather, inverse F2, conj twiddle) -> S; B: column C2R of length F1 -> out
 // Cost: two reads + two writes of the array at 60-80 % of the HBM roofline each, against one pass of
 // 16-32 byte row segments at 15-25 % (8192-long f32 lanes).
 template <typename T>
@@ -402,13 +445,13 @@ static int col_split(const Problem &P, const void *d_in, void *d_out, const FftC
             // B: twiddle on load, length F2 over b, rows k1 + F1 k2 (R2C: Hermitian row map)
             a.in = S; a.out = out_c;
             a.outer_in = (int64_t)F2 * Cp; a.outer_out = 0; a.elem_in = Cp; a.elem_out = (int64_t)F1 * I;
-            if ((rc = launch_colsplit<T>(r2c ? 2 : 1, inv, a, stream))) return rc;
+            if ((rc = launch_colsplit<T>(r2c ? CS_R2C_2 : CS_C2C, inv, a, stream))) return rc;
         } else {
             // A: Hermitian gather, inverse of length F2 over k2, conj twiddle -> S[o][k1][b][i]
             a.in = in_c; a.out = S;
             a.outer_in = 0; a.outer_out = (int64_t)F2 * Cp; a.elem_in = I; a.elem_out = Cp;
             a.stream_in = (int)NDFFT_DEV_INT("NDFFT_CS3_NT", 1);
-            if ((rc = launch_colsplit<T>(3, true, a, stream))) return rc;
+            if ((rc = launch_colsplit<T>(CS_C2R_1, true, a, stream))) return rc;
             a.stream_in = 0;
             // B: column C2R of length F1 over k1
             Q.op = NDFFT_OP_C2R; Q.xlen = K1; Q.ylen = F1; Q.xs = (int64_t)F2 * Cp; Q.ys = (int64_t)F2 * I;
@@ -467,34 +510,26 @@ static int big_fft(const FftConfig &c, const DevConfig &d, const cpx<T> *zin, in
     //   (2) length-F2 FFTs over n2 of s1 (stride F1, adjacent k1 contiguous), twiddle W_F^(n2 k1) on load, stored at
     //       k1 + F1 k2 = natural order.   256 x 65536 c128: 317 us (three passes) -> see DESIGN.md section 3.5
     // (round 6: a smooth NON-power-of-two factor runs the same two passes on kernels specialised with hiprtc -- jit.hip: launch_jit_fourstep -- instead of the six-pass transpose route)
-    const int dti = dtype_of<T>();
-    const FftConfig &sc1 = c.sub1->cfg[CFG_MAIN], &sc2 = c.sub2->cfg[CFG_MAIN];
-    const FsPass kind1 = fs_pass(F1, !sc1.twp_col.re.empty(), sc1.fs_jit, jit_fourstep_ok, dti, sc1.fs_jitcfg);
-    const FsPass kind2 = fs_pass(F2, !sc2.twp_col.re.empty(), sc2.fs_jit, jit_fourstep_ok, dti, sc2.fs_jitcfg);
+    const FsPlan p1 = fs_plan(FS_CPX_1, F1, c.sub1, dtype_of<T>()), p2 = fs_plan(FS_CPX_2, F2, c.sub2, dtype_of<T>());
     // (a declined hiprtc pass falls through to the forms below: only the scratch s1 has been written, zout is untouched)
-    if (kind1 && kind2 && fourstep2_enabled()) {
-        const DevTables *dt1, *dt2;
-        if ((rc = get_dev_tables(c.sub1, &dt1)) || (rc = get_dev_tables(c.sub2, &dt2))) return rc;
+    if (p1 && p2 && fourstep2_enabled()) {
         RealArgs<T> a = fs_args<T>(d.twlo, d.twhi, c.logB, 1, F1, F);
         // (used by the half-line tiles only, F = 1024 f32 -- pow2_real.h; 32 x 2^20 c64: 403 -> 354 us, profiles/r06)
         a.xcd_chunk = (int)NDFFT_DEV_INT("NDFFT_FS_XCD_CHUNK", 32);
         // pass 1: lanes (l, n2)
         a.in = zin; a.out = s1; a.nlanes = L * F2; a.n = F1; a.F = F1; a.n_in = F1; a.n_out = F1; a.scale = (T)1;
         a.inner = F2; a.outer_in = pitch_in; a.elem_in = F2; a.pitch_out = K1p;
-        const bool w1 = kind1 == FS_AOT && fourstep_wide(dti, 1, F1) && dt1->cfg[CFG_MAIN].twp_col_w, w2 = kind2 == FS_AOT && fourstep_wide(dti, 2, F2) && dt2->cfg[CFG_MAIN].twp_col_w;
-        a.twp = (const cpx<T> *)(kind1 == FS_RTC ? dt1->cfg[CFG_MAIN].twp_fs : w1 ? dt1->cfg[CFG_MAIN].twp_col_w : dt1->cfg[CFG_MAIN].twp_col); a.wide = w1 ? 1 : 0;
         // c128 (the lane-fastest kernels): the caller's array is read once -> streaming loads; the intermediate is re-read by pass 2 -> cache-allocating stores.
         // A-B-A-B (profiles/r08/r08s_fourstep_pass1_policy_abab.txt): 256 x 65536 203 -> 197 us, 16 x 2^20 260 -> 248 us; either one alone is neutral or worse
         // (keep alone: 213 us); c64 (staged kernels) 285 -> 291 us with the streaming loads: off there
         a.stream_in = (int)NDFFT_DEV_INT("NDFFT_FS_P1_NT", sizeof(T) == 8 ? 1 : 0); a.keep_out = (int)NDFFT_DEV_INT("NDFFT_FS_KEEP", sizeof(T) == 8 ? 1 : 0);
-        rc = kind1 == FS_RTC ? jit_rc(launch_jit_fourstep<T>(1, inverse, sc1.fs_jitcfg, a, stream)) : launch_fourstep<T>(1, F1, inverse, a, stream);
+        rc = fs_launch<T>(p1, inverse, a, stream);
         if (rc == NDFFT_OK) {
             a.stream_in = 0; a.keep_out = 0;
             // pass 2: lanes (l, k1)
             a.in = s1; a.out = zout; a.nlanes = L * F1; a.n = F2; a.F = F2; a.n_in = F2; a.n_out = F2; a.scale = scale;
             a.inner = F1; a.outer_in = (int64_t)F2 * K1p; a.outer_out = pitch_out; a.elem_in = K1p; a.elem_out = F1; a.pitch_out = 0;
-            a.twp = (const cpx<T> *)(kind2 == FS_RTC ? dt2->cfg[CFG_MAIN].twp_fs : w2 ? dt2->cfg[CFG_MAIN].twp_col_w : dt2->cfg[CFG_MAIN].twp_col); a.wide = w2 ? 1 : 0;
-            rc = kind2 == FS_RTC ? jit_rc(launch_jit_fourstep<T>(2, inverse, sc2.fs_jitcfg, a, stream)) : launch_fourstep<T>(2, F2, inverse, a, stream);
+            rc = fs_launch<T>(p2, inverse, a, stream);
         }
         if (rc != kDeclined) return rc;
     }
@@ -559,25 +594,20 @@ static int real_fourstep(const Problem &P, int gop, const FftConfig &c, const De
     // natural pitch N1/2 + 1 every tile row would straddle two lines shared with a tile on another XCD)
     const int K = (N1 / 2 + 1 + (int)(128 / sizeof(cpx<T>)) - 1) & ~((int)(128 / sizeof(cpx<T>)) - 1);
     const int64_t n = (int64_t)N1 * N2, B = P.nlanes;
-    const DevTables *dt1, *dt2;
+    const DevTables *dt1;
     int rc;
     // (round 6: a factor that is not a power of two runs its pass on a kernel specialised with hiprtc -- plan.hip: add_real_fourstep_smooth; declined before
     //  anything is launched when that is not to be had: the caller falls back to the packed route)
-    const int dti = dtype_of<T>();
-    const FftConfig &rc1 = c.rfs_sub1->cfg[CFG_MAIN], &rc2 = c.rfs_sub2->cfg[CFG_MAIN];
-    const FsPass p1 = fs_pass(N1 / 2, true, rc1.jit, jit_rfs1_ok, dti, rc1.jitcfg);
-    if (!p1) return kDeclined;
-    const FsPass p2 = fs_pass(N2, true, rc2.fs_jit, jit_fourstep_ok, dti, rc2.fs_jitcfg);
-    if (!p2) return kDeclined;
-    const bool jit1 = p1 == FS_RTC, jit2 = p2 == FS_RTC;
-    if ((rc = get_dev_tables(c.rfs_sub1, &dt1)) || (rc = get_dev_tables(c.rfs_sub2, &dt2))) return rc;
+    const FsPlan p1 = fs_plan(FS_REAL_1, N1 / 2, c.rfs_sub1, dtype_of<T>()), p2 = fs_plan(gop == G_DCT2_EVEN ? FS_DCT2_2 : FS_HALF_2, N2, c.rfs_sub2, dtype_of<T>());
+    if (!p1 || !p2) return kDeclined;
+    if ((rc = get_dev_tables(c.rfs_sub1, &dt1))) return rc;
     void *s1;
     if ((rc = get_scratch(4, stream, (size_t)(B * N2 * K) * sizeof(cpx<T>), &s1))) return rc;
     RealArgs<T> a = fs_args<T>(d.rfs_twlo, d.rfs_twhi, c.rfs_logB, 1, N1, n);
     // pass 1: lanes (l, n2), real input
     a.in = d_in; a.out = s1; a.nlanes = B * N2; a.n = N1; a.F = N1 / 2; a.n_in = N1; a.n_out = N1 / 2 + 1; a.scale = (T)1;
     a.inner = N2; a.outer_in = pin; a.elem_in = N2; a.pitch_out = K;
-    a.aux1 = (const cpx<T> *)dt1->cfg[CFG_MAIN].aux1; a.twp = (const cpx<T> *)dt1->cfg[CFG_MAIN].twp;
+    a.aux1 = (const cpx<T> *)dt1->cfg[CFG_MAIN].aux1;
     a.makhoul = gop == G_DCT2_EVEN ? 1 : dct1 ? 3 : 0;
     // streaming loads of the caller's lane in pass 1: R2C re-read 123.5 -> 118 us (HBM-sourced unchanged); not for DCT-II, whose mirror tiles share every line
     // (134 -> 144 us) -- profiles/r08/r08t_real_fourstep_policy_abab.txt
@@ -590,7 +620,7 @@ static int real_fourstep(const Problem &P, int gop, const FftConfig &c, const De
         const bool resident = row_load_policy(d_in, (size_t)B * (dct1 ? (size_t)(n / 2 + 1) : (size_t)n) * es, d_out, (size_t)B * (size_t)(gop == G_R2C_EVEN ? (n / 2 + 1) * 2 : dct1 ? n / 2 + 1 : n) * es) == 0;
         a.stream_in = (gop == G_DCT2_EVEN || dct1) ? 0 : (knob == 2 ? (resident ? 1 : 0) : (int)knob);     // (DCT-I reads every element twice, through its own tile and the mirrored one)
     }
-    if ((rc = jit1 ? jit_rc(launch_jit_fourstep<T>(11, false, rc1.jitcfg, a, stream)) : launch_fourstep_real<T>(1, N1 / 2, a, stream))) return rc;
+    if ((rc = fs_launch<T>(p1, false, a, stream))) return rc;
     a.stream_in = 0;
     // pass 2: lanes (l, k1)
     a.makhoul = dct1 ? 3 : 0;                        // (3: real outputs Re X[k] a.scale)
@@ -598,10 +628,9 @@ static int real_fourstep(const Problem &P, int gop, const FftConfig &c, const De
     a.xcd_chunk = (int)NDFFT_DEV_INT("NDFFT_RFS_XCD_CHUNK", 8);
     a.in = s1; a.out = d_out; a.nlanes = B * K; a.n = N2; a.F = N2; a.n_in = N2; a.n_out = N2; a.scale = dct1 ? (T)(0.5 * P.scale) : (T)P.scale;
     a.inner = K; a.outer_in = (int64_t)N2 * K; a.outer_out = pout; a.elem_in = K; a.pitch_out = 0;
-    a.aux1 = nullptr; a.aux2 = (const cpx<T> *)d.aux2; a.twp = (const cpx<T> *)(jit2 ? dt2->cfg[CFG_MAIN].twp_fs : dt2->cfg[CFG_MAIN].twp_col);
+    a.aux1 = nullptr; a.aux2 = (const cpx<T> *)d.aux2;
     if (gop == G_DCT2_EVEN && NDFFT_DEV_INT("NDFFT_RFS_FACTORED", 1)) { a.fc1 = (const cpx<T> *)d.rfs_c1; a.fc2 = (const cpx<T> *)d.rfs_c2; }
-    if (jit2) return jit_rc(launch_jit_fourstep<T>(gop == G_DCT2_EVEN ? 13 : 12, false, rc2.fs_jitcfg, a, stream));
-    return launch_fourstep_real<T>(gop == G_DCT2_EVEN ? 3 : 2, N2, a, stream);
+    return fs_launch<T>(p2, false, a, stream);
 }
 
 // The inverse direction of the real four-step, C2R and DCT-III:
@@ -614,21 +643,15 @@ static int real_fourstep_inv(const Problem &P, int gop, const FftConfig &c, cons
     const int N1 = c.rfs_N1, N2 = c.rfs_N2, Kx = N1 / 2 + 1;
     const int Kp = (Kx + (int)(128 / sizeof(cpx<T>)) - 1) & ~((int)(128 / sizeof(cpx<T>)) - 1);   // lanes per o, padded: every tile starts on a 128-byte line of the input
     const int64_t n = (int64_t)N1 * N2, B = P.nlanes;
-    const DevTables *dt2;
     int rc;
     // (round 6: N2 not a power of two -> pass 1 on the hiprtc form of the lane-fastest kernel; N1 / 2 not a power of two -> pass 2 through dispatch(): the general column C2R kernel, hiprtc too)
-    const int dti = dtype_of<T>();
-    const FftConfig &rc2 = c.rfs_sub2->cfg[CFG_MAIN];
-    const FsPass p1 = fs_pass(N2, true, rc2.fs_jit, jit_rfsi_ok, dti, rc2.fs_jitcfg);
+    const FsPlan p1 = fs_plan(gop == G_DCT3_EVEN ? FS_DCT3_1 : FS_C2R_1, N2, c.rfs_sub2, dtype_of<T>());
     if (!p1) return kDeclined;
-    const bool jit2 = p1 == FS_RTC, aot1 = fourstep_supported(N1 / 2);
     // DCT-III writes its outputs through the inverse of Makhoul's permutation in the LAST pass: only the column-tile kernels do that (RealArgs::makhoul), and dispatch() may
     // pick another kernel for a length that is not a power of two (a small call runs the generic kernel) -- so DCT-III needs the ahead-of-time last pass
-    const FftConfig &rc1 = c.rfs_sub1->cfg[CFG_MAIN];
-    FsPass last = FS_NONE;   // ... or the hiprtc column tile of that length, launched HERE (not through dispatch(), which may pick another kernel for a small call)
-    if (gop == G_DCT3_EVEN && !(last = fs_pass(N1 / 2, true, rc1.jit, jit_col_ok, dti, rc1.jitcfg))) return kDeclined;
-    const bool jit_last = last == FS_RTC;
-    if ((rc = get_dev_tables(c.rfs_sub2, &dt2))) return rc;
+    // ... or the hiprtc column tile of that length, launched HERE.  C2R takes the tile pass only in its ahead-of-time form.
+    const FsPlan last = gop == G_DCT3_EVEN || fourstep_supported(N1 / 2) ? fs_plan(FS_C2R_LAST, N1 / 2, c.rfs_sub1, dtype_of<T>()) : FsPlan();
+    if (gop == G_DCT3_EVEN && !last) return kDeclined;
     void *s1;
     // (no pitch padding here: with + 128 B per row ndifft_r2c 64 x 262144 f64 measured 112 -> 118 us, nddct3 unchanged -- profiles/r08/r08k_longlanes_pad.txt)
     const int64_t N2p = N2;                          // pitch of the intermediate s[k1][n2]
@@ -637,24 +660,22 @@ static int real_fourstep_inv(const Problem &P, int gop, const FftConfig &c, cons
     a.aux2 = (const cpx<T> *)d.aux2;
     a.in = d_in; a.out = s1; a.nlanes = B * Kp; a.n = N2; a.F = N2; a.n_in = N2; a.n_out = N2; a.scale = (T)P.scale;
     a.inner = Kp; a.outer_in = pin; a.elem_in = N1; a.pitch_out = N2p;
-    a.twp = (const cpx<T> *)(jit2 ? dt2->cfg[CFG_MAIN].twp_fs : dt2->cfg[CFG_MAIN].twp_col);
     // runs of consecutive tiles per XCD: the mirrored index N1 - k1 is shifted by one element against the tile grid (and DCT-III's real rows are
     // half lines), so neighbouring tiles share every line
     a.xcd_chunk = (int)NDFFT_DEV_INT("NDFFT_RFS_XCD_CHUNK", 8);
     a.stream_in = (int)NDFFT_DEV_INT("NDFFT_RFSI_P1_NT", 0);      // (measured: ndifft_r2c re-read 112 -> 125 us with streaming loads of the half spectrum: off)
     if (gop == G_DCT3_EVEN && NDFFT_DEV_INT("NDFFT_RFS_FACTORED", 1)) { a.fc1 = (const cpx<T> *)d.rfs_c1; a.fc2 = (const cpx<T> *)d.rfs_c2; }
-    if ((rc = jit2 ? jit_rc(launch_jit_fourstep<T>(gop == G_DCT3_EVEN ? 15 : 14, false, rc2.fs_jitcfg, a, stream)) : launch_fourstep_real<T>(gop == G_DCT3_EVEN ? 5 : 4, N2, a, stream))) return rc;
+    if ((rc = fs_launch<T>(p1, false, a, stream))) return rc;
     a.stream_in = 0;
-    if ((sw().rfs_c2r_tile && aot1) || jit_last) {   // the column C2R kernel on 128-byte tiles (0: the general column kernel through dispatch())
+    if (last.how == FS_RTC || (last.how == FS_AOT && sw().rfs_c2r_tile)) {   // the column C2R kernel on 128-byte tiles (0: the general column kernel through dispatch())
         const DevTables *dt1;
         if ((rc = get_dev_tables(c.rfs_sub1, &dt1))) return rc;
         a.xcd_chunk = 0; a.keep_out = 0; a.fc1 = nullptr; a.fc2 = nullptr;
         a.in = s1; a.out = d_out; a.nlanes = B * N2; a.n = N1; a.F = N1 / 2; a.n_in = Kx; a.n_out = N1; a.scale = (T)1;
         a.inner = N2; a.outer_in = (int64_t)Kx * N2p; a.outer_out = pout; a.elem_in = N2p; a.elem_out = N2; a.pitch_in = 0; a.pitch_out = 0;
-        a.aux1 = (const cpx<T> *)dt1->cfg[CFG_MAIN].aux1; a.twp = (const cpx<T> *)dt1->cfg[CFG_MAIN].twp;
+        a.aux1 = (const cpx<T> *)dt1->cfg[CFG_MAIN].aux1;
         a.makhoul = gop == G_DCT3_EVEN ? 1 : 0;
-        if (jit_last) return jit_rc(launch_jit_real<T>(G_C2R_EVEN, rc1.jitcfg, true, a, stream));
-        return launch_fourstep_real<T>(7, N1 / 2, a, stream);
+        return fs_launch<T>(last, false, a, stream);
     }
     Problem Q;
     Q.plan = c.rfs_sub1; Q.op = NDFFT_OP_C2R; Q.xlen = Kx; Q.ylen = N1; Q.xs = N2p; Q.ys = N2; Q.nlanes = B * N2; Q.scale = 1.0;
@@ -667,12 +688,10 @@ static int real_fourstep_inv(const Problem &P, int gop, const FftConfig &c, cons
 // DCT-IV of a long even lane, n = 2 F, F = F1 * F2 powers of two: the complex four-step of length F with the fold z[j] = (x[2j] + i x[n-1-2j]) s w_j built by
 // pass 1's load and the outputs y[2k] = Re(Z[k] c_k), y[n-1-2k] = -Im(Z[k] c_k) written by pass 2's store -- two passes instead of four.
 template <typename T>
-static int dct4_fourstep(const Problem &P, const FftConfig &c, const DevConfig &d, const void *d_in, void *d_out, int64_t pin, int64_t pout, hipStream_t stream, bool jit1 = false, bool jit2 = false) {
+static int dct4_fourstep(const Problem &P, const FftConfig &c, const DevConfig &d, const void *d_in, void *d_out, int64_t pin, int64_t pout, hipStream_t stream, const FsPlan &p1, const FsPlan &p2) {
     const int F1 = c.F1, F2 = c.F2;
     const int64_t F = (int64_t)F1 * F2, B = P.nlanes;
-    const DevTables *dt1, *dt2;
     int rc;
-    if ((rc = get_dev_tables(c.sub1, &dt1)) || (rc = get_dev_tables(c.sub2, &dt2))) return rc;
     void *s1;
     const int64_t K1p = F1 + fs_pad_elems<T>();      // pitch of the intermediate s1[n2][k1] (fs_pad_elems)
     if ((rc = get_scratch(2, stream, (size_t)(B * F2 * K1p) * sizeof(cpx<T>), &s1))) return rc;
@@ -681,19 +700,17 @@ static int dct4_fourstep(const Problem &P, const FftConfig &c, const DevConfig &
     // pass 1: lanes (l, n2) of the REAL input
     a.in = d_in; a.out = s1; a.nlanes = B * F2; a.n = F1; a.F = F1; a.n_in = F1; a.n_out = F1; a.scale = (T)P.scale;
     a.inner = F2; a.outer_in = pin; a.elem_in = F2; a.pitch_out = K1p;
-    a.twp = (const cpx<T> *)(jit1 ? dt1->cfg[CFG_MAIN].twp_fs : dt1->cfg[CFG_MAIN].twp_col); a.makhoul = 2;
+    a.makhoul = 2;
     // pass 1: streaming loads of the caller's lane, cache-allocating stores of the intermediate (the staged ROWOUT store ignored keep_out until round 5):
     // nddct4 64 x 262144 f64 157.6 -> 153.3 (stores) -> 148-150 us (both)
     a.stream_in = (int)NDFFT_DEV_INT("NDFFT_DCT4_P1_NT", 1); a.keep_out = (int)NDFFT_DEV_INT("NDFFT_DCT4_KEEP", 1);
-    if ((rc = jit1 ? jit_rc(launch_jit_fourstep<T>(1, false, c.sub1->cfg[CFG_MAIN].fs_jitcfg, a, stream)) : launch_fourstep<T>(1, F1, false, a, stream))) return rc;
+    if ((rc = fs_launch<T>(p1, false, a, stream))) return rc;
     a.stream_in = 0;
     // pass 2: lanes (l, k1), real output
     a.makhoul = 0; a.keep_out = 0;
     a.in = s1; a.out = d_out; a.nlanes = B * F1; a.n = F2; a.F = F2; a.n_in = F2; a.n_out = F2; a.scale = (T)1;
     a.inner = F1; a.outer_in = (int64_t)F2 * K1p; a.outer_out = pout; a.elem_in = K1p; a.elem_out = 0; a.pitch_out = 0;
-    a.twp = (const cpx<T> *)(jit2 ? dt2->cfg[CFG_MAIN].twp_fs : dt2->cfg[CFG_MAIN].twp_col);
-    if (jit2) return jit_rc(launch_jit_fourstep<T>(16, false, c.sub2->cfg[CFG_MAIN].fs_jitcfg, a, stream));
-    return launch_fourstep_real<T>(6, F2, a, stream);
+    return fs_launch<T>(p2, false, a, stream);
 }
 
 // contiguous lanes whose inner FFT does not fit one workgroup's LDS
@@ -719,11 +736,8 @@ static int dispatch_big(const Problem &P, const void *d_in, void *d_out, const D
         rc = real_fourstep<T>(P, gop, c, d, d_in, d_out, pin, pout, stream);
     } else if (gop == G_DCT4_EVEN && rfs_on && c.big && !c.bigblue && fourstep2_enabled()) {
         // (round 6: a factor that is not a power of two on the hiprtc forms of the same two kernels -- pass 1 the staged ROWOUT kernel, pass 2 the lane-fastest one, whole rounds)
-        const int dti = dtype_of<T>();
-        const FftConfig &s1c = c.sub1->cfg[CFG_MAIN], &s2c = c.sub2->cfg[CFG_MAIN];
-        const FsPass k1 = fs_pass(c.F1, !s1c.twp_col.re.empty(), s1c.fs_jit, jit_fourstep_ok, dti, s1c.fs_jitcfg);
-        const FsPass k2 = k1 ? fs_pass(c.F2, !s2c.twp_col.re.empty(), s2c.fs_jit, jit_rfsi_ok, dti, s2c.fs_jitcfg) : FS_NONE;
-        if (k2) rc = dct4_fourstep<T>(P, c, d, d_in, d_out, pin, pout, stream, k1 == FS_RTC, k2 == FS_RTC);
+        const FsPlan p1 = fs_plan(FS_CPX_1, c.F1, c.sub1, dtype_of<T>()), p2 = p1 ? fs_plan(FS_DCT4_2, c.F2, c.sub2, dtype_of<T>()) : FsPlan();
+        if (p2) rc = dct4_fourstep<T>(P, c, d, d_in, d_out, pin, pout, stream, p1, p2);
     } else if (c.rfs && ((gop == G_C2R_EVEN && (rfs_ops & 2)) || (gop == G_DCT3_EVEN && (rfs_ops & 8)))) {
         rc = real_fourstep_inv<T>(P, gop, c, d, d_in, d_out, pin, pout, stream);
     }

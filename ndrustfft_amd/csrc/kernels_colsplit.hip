@@ -40,15 +40,15 @@ template <typename T, int OP, int CS> static int launch_cs(const RealArgs<T> &a,
 int colsplit_inner_len() { return 64; }
 int colsplit_tile_lanes() { return kCsLPB; }
 
-template <typename T> int launch_colsplit(int cs, bool inverse, const RealArgs<T> &a, hipStream_t s) {
-    switch (cs) {
-        case 1: return inverse ? launch_cs<T, G_C2C_INV, 1>(a, s) : launch_cs<T, G_C2C_FWD, 1>(a, s);
-        case 2: return launch_cs<T, G_C2C_FWD, 2>(a, s);
-        case 3: return launch_cs<T, G_C2C_INV, 3>(a, s);
-        default: return fail(NDFFT_ERR_INVALID_ARG, "column four-step: bad stage kind");
+template <typename T> int launch_colsplit(CsStage stage, bool inverse, const RealArgs<T> &a, hipStream_t s) {
+    switch (stage) {
+        case CS_C2C: return inverse ? launch_cs<T, G_C2C_INV, CS_C2C>(a, s) : launch_cs<T, G_C2C_FWD, CS_C2C>(a, s);
+        case CS_R2C_2: return launch_cs<T, G_C2C_FWD, CS_R2C_2>(a, s);
+        case CS_C2R_1: return launch_cs<T, G_C2C_INV, CS_C2R_1>(a, s);
     }
+    return fail(NDFFT_ERR_INVALID_ARG, "column four-step: bad stage kind");
 }
-template int launch_colsplit<float>(int, bool, const RealArgs<float> &, hipStream_t);
-template int launch_colsplit<double>(int, bool, const RealArgs<double> &, hipStream_t);
+template int launch_colsplit<float>(CsStage, bool, const RealArgs<float> &, hipStream_t);
+template int launch_colsplit<double>(CsStage, bool, const RealArgs<double> &, hipStream_t);
 
 }  // namespace ndfft

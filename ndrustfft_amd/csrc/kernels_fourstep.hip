@@ -97,7 +97,7 @@ bool fourstep_supported(int F) { return F == 64 || F == 128 || F == 256 || F == 
 using WideRL = RadixList<16, 8, 8>;
 static constexpr int kWideTPL = 64;
 void fourstep_build_wide_twiddles(int F, HostTable &out) { if (F == 1024) build_tw<WideRL>(out); }
-bool fourstep_wide(int dtype, int pass, int F) {
+bool fourstep_wide(int dtype, FsPass pass, int F) {
     if (F != 1024) return false;
     const long k = NDFFT_DEV_INT("NDFFT_FS_WIDE", 1);          // developer build: 0 = off (A/B)
     if (!k || sw().fs_direct == 0) return false;
@@ -119,19 +119,20 @@ template <typename T, int OP, int MODE> static int launch_fsd_wide(const RealArg
     return NDFFT_OK;
 }
 
-// pass = 1: column load / row store; pass = 2: twiddle by the inner index on load, column store
-template <typename T> int launch_fourstep(int pass, int F, bool inverse, const RealArgs<T> &a, hipStream_t s) {
+// FS_CPX_1: column load / row store (staged: ROWOUT, lane-fastest: mode 0); FS_CPX_2: twiddle by the inner index on load, column store (CS = 4 / mode 4)
+template <typename T> int launch_fourstep(FsPass pass, int F, bool inverse, const RealArgs<T> &a, hipStream_t s) {
+    if (pass != FS_CPX_1 && pass != FS_CPX_2) return fail(NDFFT_ERR_INVALID_ARG, "row four-step: not a complex pass");
     if constexpr (sizeof(T) == 8) if (a.wide && F == 1024 && !a.makhoul) {
-        if (pass == 1) return inverse ? launch_fsd_wide<T, G_C2C_INV, 0>(a, s) : launch_fsd_wide<T, G_C2C_FWD, 0>(a, s);
+        if (pass == FS_CPX_1) return inverse ? launch_fsd_wide<T, G_C2C_INV, 0>(a, s) : launch_fsd_wide<T, G_C2C_FWD, 0>(a, s);
         return inverse ? launch_fsd_wide<T, G_C2C_INV, 4>(a, s) : launch_fsd_wide<T, G_C2C_FWD, 4>(a, s);
     }
 #define NDFFT_FS_CASE(F_)                                                                                              \
     case F_:                                                                                                           \
         if (fs_direct<T>() && !a.makhoul) {   /* (the fused DCT-IV first pass exists in the staged form only) */                \
-            if (pass == 1) return inverse ? launch_fsd<T, F_, G_C2C_INV, 0>(a, s) : launch_fsd<T, F_, G_C2C_FWD, 0>(a, s); \
+            if (pass == FS_CPX_1) return inverse ? launch_fsd<T, F_, G_C2C_INV, 0>(a, s) : launch_fsd<T, F_, G_C2C_FWD, 0>(a, s); \
             return inverse ? launch_fsd<T, F_, G_C2C_INV, 4>(a, s) : launch_fsd<T, F_, G_C2C_FWD, 4>(a, s);            \
         }                                                                                                              \
-        if (pass == 1) return inverse ? launch_fs<T, F_, G_C2C_INV, 0, true>(a, s) : launch_fs<T, F_, G_C2C_FWD, 0, true>(a, s); \
+        if (pass == FS_CPX_1) return inverse ? launch_fs<T, F_, G_C2C_INV, 0, true>(a, s) : launch_fs<T, F_, G_C2C_FWD, 0, true>(a, s); \
         return inverse ? launch_fs<T, F_, G_C2C_INV, 4, false>(a, s) : launch_fs<T, F_, G_C2C_FWD, 4, false>(a, s);
     switch (F) {
         NDFFT_FS_CASE(64) NDFFT_FS_CASE(128) NDFFT_FS_CASE(256) NDFFT_FS_CASE(512) NDFFT_FS_CASE(1024)
@@ -139,7 +140,7 @@ template <typename T> int launch_fourstep(int pass, int F, bool inverse, const R
     }
 #undef NDFFT_FS_CASE
 }
-template int launch_fourstep<float>(int, int, bool, const RealArgs<float> &, hipStream_t);
-template int launch_fourstep<double>(int, int, bool, const RealArgs<double> &, hipStream_t);
+template int launch_fourstep<float>(FsPass, int, bool, const RealArgs<float> &, hipStream_t);
+template int launch_fourstep<double>(FsPass, int, bool, const RealArgs<double> &, hipStream_t);
 
 }  // namespace ndfft
