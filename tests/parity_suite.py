@@ -8,8 +8,9 @@ import os
 import numpy as np
 
 import accuracy as acc
+import devmem
 import synth
-from helpers import TOL, assert_close, cdt_of
+from helpers import TOL, assert_close, cdt_of, rel_global, rel_lane_l2
 from ndrustfft_amd import _lib, api, handlers
 from ndrustfft_amd.handlers import Normalization
 from oracle import oracle_ctypes as orc
@@ -1239,6 +1240,178 @@ def lane_isolation(L, cases, transform=None):
                 rows = np.nonzero((lanes[0] != lanes[k]).any(axis=1))[0]
                 bad.append(f"kept lanes differ with {label} neighbours (kept-lane rows {rows[:8].tolist()}): " + what)
     assert not bad, "\n".join([f"{len(bad)} lane-isolation failures"] + bad)
+
+
+# ---- device-resident views between guard bands: where a kernel touches memory (docs/device_views.md) -----------------------------------------
+# Host arrays cannot show a store or a load outside a view: the host path copies back the view's elements only, and its staging image holds
+# whatever it held before.  Here the arrays live in device allocations  front band | image | back band ; after one ndfft_exec_device call both
+# allocations come back whole.
+GUARD_BAND = 256 << 10     # bytes per band: a multiple of 16 (the view's base alignment is the geometry's) and more than any workgroup's chunk
+# name -> (padding of the input image, padding of the output image, elements between the front band and the image); paddings in bytes (int) or
+# one element ("elem"), added to the fastest dimension of the image: the last of a C-layout array, the first of an F-layout one
+GUARD_GEOMETRIES = {"G1": (0, 0, 0),                # the case's own dense layout, 16-byte aligned base
+                    "G2": (16, 32, 0),              # pitch_in != pitch_out, every row still 16-byte aligned
+                    "G3": ("elem", "elem", 0),      # odd pitch: rows of 4- and 8-byte elements alternate between alignments
+                    "G4": (0, 0, 1),                # base one element into the allocation: only element-aligned
+                    "NEG": (0, 0, 0),               # both images stored reversed along the transform axis, the views step backwards over them
+                    "BCAST": (0, 0, 0)}             # the input's outermost batch dimension has stride 0 (np.broadcast_to), dense output
+GUARD_SPARSE = ("G3", "G4")                         # run on the first case of each (route, dtype, real / complex input) in table order
+
+
+def _nan_of(dt):
+    return complex(np.nan, np.nan) if np.dtype(dt).kind == "c" else np.nan
+
+
+def _banded(shape, dt, layout, pad, lead, fill, reverse_axis=None):
+    """(flat allocation, view of `shape` in it): band | lead elements | image whose fastest dimension is `pad` elements longer | band, all `fill`."""
+    dt = np.dtype(dt)
+    band = GUARD_BAND // dt.itemsize
+    shp = list(shape); shp[0 if layout == "F" else -1] += pad
+    nel = int(np.prod(shp))
+    flat = np.full(2 * band + lead + nel, fill, dt)
+    body = flat[band + lead:band + lead + nel].reshape(shp, order="F" if layout == "F" else "C")
+    view = body[tuple(slice(0, s) for s in shape)]
+    if reverse_axis is not None:
+        view = view[(slice(None),) * reverse_axis + (slice(None, None, -1),)]
+    assert np.shares_memory(view, flat)
+    return flat, view
+
+
+def guarded_allocs(geometry, x, sout, odt, axis, layout):
+    """(xa, xv, ya, yv) of one geometry: the input allocation (bands and padding NaN, the view holds x), the output allocation (bands and padding
+    the sentinel, the view NaN) and the two views."""
+    pad_in, pad_out, lead = GUARD_GEOMETRIES[geometry]
+    pads = [1 if p == "elem" else -(-p // np.dtype(dt).itemsize) for p, dt in ((pad_in, x.dtype), (pad_out, odt))]
+    rev = axis if geometry == "NEG" else None
+    if geometry == "BCAST":
+        b = 0 if axis != 0 else 1                           # the outermost batch dimension
+        assert (np.take(x, [0], axis=b) == x).all(), "a broadcast input repeats along its stride-0 dimension"
+        one = list(x.shape); one[b] = 1
+        xa, x1 = _banded(one, x.dtype, layout, 0, 0, _nan_of(x.dtype))
+        x1[...] = np.take(x, [0], axis=b)
+        xv = np.broadcast_to(x1, x.shape)
+    else:
+        xa, xv = _banded(x.shape, x.dtype, layout, pads[0], lead, _nan_of(x.dtype), rev)
+        xv[...] = x
+    ya, yv = _banded(sout, odt, layout, pads[1], lead, devmem.SENTINEL, rev)
+    yv[...] = _nan_of(odt)
+    return xa, xv, ya, yv
+
+
+def _exec_device_banded(L, h, name, xa, xv, ya, yv, axis):
+    """One ndfft_exec_device call (NORM_DEFAULT, null stream) on device images of the allocations; returns (output allocation, input allocation, route)."""
+    import ctypes
+    din, dout = devmem.DevBuf(L, xa), devmem.DevBuf(L, ya)
+    try:
+        L.check(L.c.ndfft_exec_device(h._plan, devmem.OPC[name], ctypes.c_void_p(din.p.value + devmem._off(xv, xa)), ctypes.c_void_p(dout.p.value + devmem._off(yv, ya)),
+                                      xv.ndim, api._i64(xv.shape), api._i64(devmem.strides_of(xv)), api._i64(yv.shape), api._i64(devmem.strides_of(yv)), axis,
+                                      _lib.NORM_DEFAULT, 0.0, None))
+        path = L.last_path()
+        L.check(L.c.ndfft_dev_sync(None))
+        return dout.download(ya), din.download(xa), path
+    finally:
+        din.free(); dout.free()
+
+
+def _bits(a):
+    """The elements of a as unsigned integers, one row per element (complex: two columns)."""
+    a = np.ascontiguousarray(a)
+    r = a.view(a.real.dtype).reshape(a.size, -1)
+    return r.view(np.uint32 if r.dtype.itemsize == 4 else np.uint64)
+
+
+def guarded_check(xa, ya, yv, got_out, got_in, yo, axis, rdt):
+    """What one call left in the two allocations: the failures, as a list of texts (empty: clean)."""
+    msgs = []
+    idx = devmem.view_index(ya, yv)
+    outside = np.ones(ya.size, bool); outside[idx.reshape(-1)] = False
+    hit = np.nonzero(outside & (_bits(got_out) != _bits(np.full(1, devmem.SENTINEL, ya.dtype))).any(axis=1))[0]
+    if hit.size:
+        rel = hit - devmem._off(yv, ya) // ya.itemsize
+        msgs.append(f"{hit.size} element(s) written outside the output view: offsets {rel[0]} .. {rel[-1]} from the view's first element (the view spans "
+                    f"{int(idx.min() - idx.flat[0])} .. {int(idx.max() - idx.flat[0])})")
+    if not np.array_equal(np.ascontiguousarray(got_in).view(np.uint8), xa.view(np.uint8)):
+        diff = np.nonzero((_bits(got_in) != _bits(xa)).any(axis=1))[0]
+        msgs.append(f"{diff.size} element(s) of the input allocation changed, first at {diff[0]}")
+    gv = got_out[idx]
+    if not np.isfinite(gv).all():
+        msgs.append(f"{np.count_nonzero(~np.isfinite(gv))} of {gv.size} elements of the output view are not finite (skipped, or computed from memory outside the input view)")
+    else:
+        g, l = rel_global(gv, yo), rel_lane_l2(gv, yo, axis)
+        if not (g <= TOL[np.dtype(rdt)] and l <= TOL[np.dtype(rdt)]):
+            msgs.append(f"global rel {g:.3e}, lane L2 rel {l:.3e} > {TOL[np.dtype(rdt)]:.1e}")
+    return msgs
+
+
+def guarded_views(L, cases, geometries=("G1", "G2", "G3", "G4"), verbose=False, runner=None):
+    """Every case (a ROUTE_TABLE row) through ndfft_exec_device on banded device allocations, in each of `geometries` (GUARD_GEOMETRIES; those of
+    GUARD_SPARSE on the first case of each (route, dtype, real / complex input) only).  Per call: (1) every element of the output allocation outside
+    the view still holds the sentinel, bit for bit; (2) the input allocation is byte-identical to what went up; (3) the view is finite and within
+    helpers.TOL of the oracle, both metrics; (4) in G1 the call took the case's route.  All failures are collected into one message.  `runner`:
+    another way to make the call, (name, h, xa, xv, ya, yv, axis) -> (output allocation, input allocation, route); default ndfft_exec_device through
+    ctypes.  Returns (routes seen in G1, [(geometry, case, route)])."""
+    run = runner or (lambda name, h, xa, xv, ya, yv, axis: _exec_device_banded(L, h, name, xa, xv, ya, yv, axis))
+    bad, seen, records, first = [], set(), [], set()
+    for case in cases:
+        env, name, shape, axis, rdt, layout, want = case
+        n = shape[axis]
+        sin, sout = shapes_for(name, shape, axis)
+        odt = np.dtype(cdt_of(rdt) if OPS[name][4] else rdt)
+        key = (want, np.dtype(rdt), OPS[name][3])
+        geoms = [g for g in geometries if g not in GUARD_SPARSE or key not in first]
+        first.add(key)
+        x = acc.make_input("uniform", name, sin, axis, rdt, offset=n)
+        if "BCAST" in geoms:
+            b = 0 if axis != 0 else 1
+            xb = np.ascontiguousarray(np.broadcast_to(np.take(x, [0], axis=b), sin))
+        with switches(L, **env):
+            h, o = handlers_for(name, n, rdt, L)
+            yo = np.zeros(sout, odt); OPS[name][1](x, yo, o, axis)             # the oracle's result, once for every geometry
+            for g in geoms:
+                xg, yg = x, yo
+                if g == "BCAST":
+                    xg = xb
+                    yg = np.zeros(sout, odt); OPS[name][1](xb, yg, o, axis)
+                xa, xv, ya, yv = guarded_allocs(g, xg, sout, odt, axis, layout)
+                got_out, got_in, path = run(name, h, xa, xv, ya, yv, axis)
+                msgs = guarded_check(xa, ya, yv, got_out, got_in, yg, axis, rdt)
+                if g == "G1":
+                    seen.add(path)
+                    if not _route_ok(path, want):
+                        msgs.append(f"route {path} instead of {want}")
+                records.append((g, case, path))
+                line = f"{g} {path} {name} {shape} axis={axis} {np.dtype(rdt).name} {layout} {env or ''}"
+                if verbose:
+                    print(line + (": " + "; ".join(msgs) if msgs else ": clean"), flush=True)
+                bad += [line + ": " + m for m in msgs]
+    assert not bad, "\n".join([f"{len(bad)} guard-band failures"] + bad)
+    return seen, records
+
+
+def guard_route_table(records):
+    """{(route of the case, geometry): routes taken} of guarded_views' records, for the geometries whose route is recorded, not asserted."""
+    table = {}
+    for g, case, path in records:
+        if g != "G1":
+            table.setdefault((str(case[6]), g), set()).add(path)
+    return table
+
+
+def guard_extra_cases():
+    """One row case and one column case of the thread-per-lane, generic, power-of-two, hiprtc and Rader kernels, f64 and f32, for the NEG and BCAST
+    geometries.  The route field names the kernel the dense f64 shape runs on (ROUTE_TABLE); it is a label here: these views are never run in G1, and
+    the routes they do take are recorded, not asserted."""
+    no_rb = {"NDFFT_RADER": "0", "NDFFT_BLUE": "0"}
+    c = []
+    for rdt in BOTH:
+        c += _one("ndfft", (37, 7), 1, rdt, "tiny_row") + _one("ndfft", (3, 7, 70), 1, rdt, "tiny_col")
+        c += _one("nddct2", (300, 12), 1, rdt, "tinymat_row") + _one("nddct3", (9, 12, 70), 1, rdt, "tinymat_col")
+        c += _one("ndfft", (3, 1000), 1, rdt, "generic_row") + _one("ndfft", (97, 40), 0, rdt, "generic_col", env=no_rb)
+        c += _one("ndfft", (5, 2048), 1, rdt, "pow2_reg") + _one("ndfft", (64, 40), 0, rdt, "pow2_col")
+        c += _one("nddct2", (5, 128), 1, rdt, "pow2_real") + _one("ndifft_r2c", (3, 256, 17), 1, rdt, "pow2_col")
+        c += _one("ndfft", (503, 264), 1, rdt, "jit_reg") + _one("ndfft", (264, 256), 0, rdt, "jit_col")
+        c += _one("ndfft", (1356, 97), 1, rdt, "rader_reg") + _one("ndifft_r2c", (97, 1000), 0, rdt, "rader_col")
+    return c
 
 
 # ---- the case table of the MI355X run: every kernel route, and within the routes the forms listed in docs/accuracy.md ------------------------

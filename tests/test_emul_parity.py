@@ -517,3 +517,12 @@ def test_accuracy_routes(L):
 def test_lane_isolation(L):
     """The kept lanes are bit-identical whatever the other lanes hold (huge values, NaN), on every route of ROUTE_TABLE and ACC_EXTRA."""
     ps.lane_isolation(L, ROUTE_TABLE + ACC_EXTRA)
+
+
+def test_guarded_views(L):
+    """Where the kernels touch memory (parity_suite.guarded_views, docs/device_views.md): every route of ROUTE_TABLE and ACC_EXTRA through ndfft_exec_device on
+    device allocations with a guard band on either side -- dense, padded rows with pitch_in != pitch_out, an odd pitch, a base one element in -- and the
+    reversed / broadcast views of guard_extra_cases.  No element outside the output view is written, the input allocation is untouched, no result depends
+    on memory outside the input view.  The emulation speaks for the index arithmetic; tests/test_gpu_parity.py for the gfx950 code."""
+    ps.guarded_views(L, ROUTE_TABLE + ACC_EXTRA)
+    ps.guarded_views(L, ps.guard_extra_cases(), geometries=("NEG", "BCAST"))

@@ -600,3 +600,66 @@ def test_lane_isolation(L, family, dt):
     """The kept lanes of every case come out bit-identical whether their neighbours hold U[-1,1), values 1e30 / 1e250 times larger, or NaN: no arithmetic
     crosses lanes (wavefront swaps with the wrong bank mask, two lanes packed into one transform, a clamped tail load landing in a live register)."""
     ps.lane_isolation(L, ps.acc_gpu_cases(family, dt))
+
+
+# ---- where the kernels touch memory: device-resident views between guard bands (parity_suite.guarded_views, docs/device_views.md) ------------------------
+_GUARD_SEEN = {}      # (family, dt) -> routes its G1 calls took (test_guarded_views_required_routes)
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("family", list(ps.ACC_GPU_FAMILIES))
+def test_guarded_views(L, family, dt):
+    """Every case of the family through ndfft_exec_device on allocations  band | image | band : dense (on the route the case names), padded rows with
+    pitch_in != pitch_out, and -- first case of each route -- an odd pitch and a base pointer one element in.  Outside the output view every element keeps
+    its sentinel, the input allocation comes back byte-identical, the view is finite (nothing skipped, nothing computed from the NaN bands) and correct."""
+    seen, records = ps.guarded_views(L, ps.acc_gpu_cases(family, dt), verbose=True)
+    _GUARD_SEEN[family, dt] = seen
+    print("routes of the padded / offset geometries:", {k: sorted(v) for k, v in sorted(ps.guard_route_table(records).items())})
+
+
+def test_guarded_views_extra(L):
+    """The same checks on views that step backwards along the transform axis (both sides) and on an input whose outermost batch dimension has stride 0."""
+    _, records = ps.guarded_views(L, ps.guard_extra_cases(), geometries=("NEG", "BCAST"), verbose=True)
+    print("routes of the reversed / broadcast views:", {k: sorted(v) for k, v in sorted(ps.guard_route_table(records).items())})
+
+
+def _guard_torch_cases():
+    """The first row case and the first column case of every family and dtype."""
+    out = []
+    for family in ps.ACC_GPU_FAMILIES:
+        for dt in ("f64", "f32"):
+            cases = ps.acc_gpu_cases(family, dt)
+            for col in (False, True):
+                out += [c for c in cases if c[5] == "C" and (c[3] != len(c[2]) - 1) == col][:1]
+    return out
+
+
+def test_guarded_views_torch(L):
+    """The banded construction on torch tensors through the public functions: a flat torch.full buffer per side, torch.as_strided views with the
+    geometry's storage offset and strides, the call on the current stream -- api.py's stride and offset plumbing, which the ctypes calls above bypass."""
+    import torch
+
+    def tensor_of(a, v):
+        t = torch.full((a.size,), ps._nan_of(a.dtype) if np.isnan(a.flat[0]) else float(a.flat[0].real), dtype=getattr(torch, a.dtype.name), device="cuda:0")
+        tv = torch.as_strided(t, v.shape, [s // v.itemsize for s in v.strides], (v.__array_interface__["data"][0] - a.__array_interface__["data"][0]) // a.itemsize)
+        tv.copy_(torch.from_numpy(np.ascontiguousarray(v)))
+        assert t.data_ptr() % 16 == 0                  # (the view's alignment is the geometry's)
+        return t, tv
+
+    def run(name, h, xa, xv, ya, yv, axis):
+        (xt, xtv), (yt, ytv) = tensor_of(xa, xv), tensor_of(ya, yv)
+        ps.OPS[name][0](xtv, ytv, h, axis)
+        path = L.last_path()
+        torch.cuda.synchronize()
+        return yt.cpu().numpy(), xt.cpu().numpy(), path
+    ps.guarded_views(L, _guard_torch_cases(), geometries=("G1", "G2"), verbose=True, runner=run)
+
+
+def test_guarded_views_required_routes(L):
+    """The dense (G1) calls of the guard-band families together ran every kernel route (a family that has not run in this session runs here)."""
+    for family in ps.ACC_GPU_FAMILIES:
+        for dt in ("f64", "f32"):
+            if (family, dt) not in _GUARD_SEEN:
+                _GUARD_SEEN[family, dt] = ps.guarded_views(L, ps.acc_gpu_cases(family, dt), geometries=("G1",))[0]
+    seen = set().union(*_GUARD_SEEN.values())
+    assert ps.ACC_REQUIRED_ROUTES <= seen, sorted(ps.ACC_REQUIRED_ROUTES - seen)
