@@ -1,6 +1,6 @@
 /*
  * ndfft_mi355x_ext.h -- entry points added to libndfft_mi355x.so after the core header was frozen for its C99 consumers
- * (ABI minor 4).  C99; includes ndfft_mi355x.h.
+ * (ABI minor 4: the weighted call; minor 5: the filter).  C99; includes ndfft_mi355x.h.
  *
  * Normalization::Weights(w): a DIAGONAL normalisation -- a different factor per element of the lane (orthonormal DCT
  * scalings, DCT-I end-point factors, spectral filters, de-aliasing masks).  Unlike Normalization::Custom(fn), a host
@@ -38,6 +38,33 @@ int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in,
                                const int64_t *shape_in, const int64_t *stride_in,
                                const int64_t *shape_out, const int64_t *stride_out,
                                int axis, const void *d_weights, size_t n_weights, void *stream);
+
+/* ndfft_filter: for every lane along `axis`, out = s * IFFT(w (.) FFT(in)) -- exactly what ndfft -> lane *= w -> ndifft give under the normalisation `norm`
+ * (s = 1 for NDFFT_NORM_NONE, 1 / n for NDFFT_NORM_DEFAULT, `scale` for NDFFT_NORM_SCALE), in one call.  The building block of spectral derivatives, de-aliasing
+ * masks, filters, circular convolutions and Helmholtz solves along a periodic axis.
+ *
+ *   C2C plan   in, out: Complex<T>, lane length n, one `shape`, a stride vector each;   d_weights: n x Complex<T>
+ *   R2C plan   in, out: REAL T, lane length n; meaning ndfft_r2c -> *= w -> ndifft_r2c, so Im(DC) and, for even n, Im(Nyquist) of the product are dropped as
+ *              C2R always drops them;                                                   d_weights: (n / 2 + 1) x Complex<T>
+ *   DCT plan   NDFFT_ERR_INVALID_ARG
+ *
+ * Checks: those of ndfft_exec_device for the plan's forward op, with the same panic texts in the same order; then a NULL d_weights, then n_weights (the message
+ * names both numbers), then unknown bits in `flags` (all NDFFT_ERR_INVALID_ARG).  A refused call launches nothing and writes nothing.
+ * d_in == d_out with identical strides is the in-place filter and is safe on every route; any other overlap is undefined, as for ndfft_exec_device.
+ * Asynchronous on `stream`; d_weights is read on `stream`.
+ *
+ * Routes (ndfft_last_path):
+ *   "filter_pow2"                      C2C plan, n = 64 .. 4096 a power of two, lanes on which ndfft_exec_device would run "pow2_reg" (unit stride along the axis in
+ *                                      both arrays, lanes at a uniform pitch): ONE kernel, one read and one write of device memory per point, no scratch memory.
+ *                                      Nothing is allocated except, at the first call of a plan whose radix list is no palindrome (f64 128, 1024, 2048; f32 2048), a
+ *                                      second twiddle table: every other length can be captured into a HIP graph without a warm-up call.
+ *   "<fwd route>+weights+<inv route>"  everything else, and every call with NDFFT_FILTER_NO_FUSE: forward transform into a dense spectrum image kept per host thread
+ *                                      and stream, the diagonal pass in place on it, inverse transform into the output.  As for every multi-pass route the first call
+ *                                      of a size allocates: warm a shape up before capturing it. */
+#define NDFFT_FILTER_NO_FUSE 1   /* take the composed route even where a fused kernel exists (tests, A-B timing) */
+int ndfft_exec_filter_device(const ndfft_plan *plan, const void *d_in, void *d_out, int ndim,
+                             const int64_t *shape, const int64_t *stride_in, const int64_t *stride_out, int axis,
+                             const void *d_weights, size_t n_weights, int norm, double scale, int flags, void *stream);
 
 #ifdef __cplusplus
 }

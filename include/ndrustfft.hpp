@@ -487,6 +487,38 @@ NDRUSTFFT_DEFINE(nddct3, T, T, DctHandler, NDFFT_OP_DCT3, T, true, true)        
 NDRUSTFFT_DEFINE(nddct4, T, T, DctHandler, NDFFT_OP_DCT4, T, true, true)                                      // lib.rs:827-834
 #undef NDRUSTFFT_DEFINE
 
+// ---- ndfft_filter: output = IFFT(weights (.) FFT(input)) along `axis` in one call (ndfft_exec_filter_device, include/ndfft_mi355x_ext.h) --------------------
+// What ndfft -> `lane *= weights` -> ndifft (FftHandler; n complex weights) or ndfft_r2c -> multiply -> ndifft_r2c (R2cFftHandler; real arrays, n / 2 + 1 complex
+// weights) give under the handler's normalisation, which must be None or Default.  Unit-stride power-of-two lanes of 64 .. 4096 points run one fused kernel
+// (ndfft_last_path() == "filter_pow2"), everything else transform + diagonal pass + transform; fuse = false forces that form.  `&input == &output` is the in-place
+// filter.  Asynchronous on the default stream, like the other DeviceArray calls.
+namespace detail {
+template <typename A, typename T, typename NormT>
+void filter_device(const DeviceArray<A> &input, DeviceArray<A> &output, ndfft_plan *plan, const Normalization<NormT> &norm, std::size_t axis,
+                   const DeviceArray<Complex<T>> &weights, bool fuse) {
+    if (norm.kind != Normalization<NormT>::None && norm.kind != Normalization<NormT>::Default)
+        throw Error(NDFFT_ERR_INVALID_ARG, "ndfft_filter: the handler's normalisation must be None or Default");
+    if (input.shape().size() != output.shape().size()) throw Error(NDFFT_ERR_INVALID_ARG, "input and output must have the same dimensionality D");
+    if (axis > 0x7fffffffu) throw Panic(NDFFT_ERR_AXIS, "index out of bounds");
+    if (axis < input.shape().size() && input.shape() != output.shape()) throw Panic(NDFFT_ERR_SHAPE_MISMATCH, "ndfft_filter: input and output shapes differ");
+    std::size_t nw = 1;
+    for (auto e : weights.shape()) nw *= (std::size_t)e;
+    check(ndfft_exec_filter_device(plan, input.ptr(), output.ptr(), (int)input.shape().size(), input.shape().data(), input.strides().data(), output.strides().data(),
+                                   (int)axis, weights.ptr(), nw, norm.kind == Normalization<NormT>::Default ? NDFFT_NORM_DEFAULT : NDFFT_NORM_NONE, 0.0,
+                                   fuse ? 0 : NDFFT_FILTER_NO_FUSE, nullptr));
+}
+}  // namespace detail
+template <typename T>
+void ndfft_filter(const DeviceArray<Complex<T>> &input, DeviceArray<Complex<T>> &output, const FftHandler<T> &handler, std::size_t axis,
+                  const DeviceArray<Complex<T>> &weights, bool fuse = true) {
+    detail::filter_device<Complex<T>, T>(input, output, handler.plan(), handler.norm(), axis, weights, fuse);
+}
+template <typename T>
+void ndfft_filter(const DeviceArray<T> &input, DeviceArray<T> &output, const R2cFftHandler<T> &handler, std::size_t axis, const DeviceArray<Complex<T>> &weights,
+                  bool fuse = true) {
+    detail::filter_device<T, T>(input, output, handler.plan(), handler.norm(), axis, weights, fuse);
+}
+
 /// Selects the GPUs the `_par` functions spread one call over (ids as ndfft_set_device numbers them).
 inline void set_par_devices(std::vector<int> ids) { detail::par_devices_ref() = std::move(ids); }
 

@@ -29,6 +29,9 @@ SYMBOLS = [
 ]
 # the entry points of include/ndfft_mi355x_ext.h (ABI minor 4 on): added after the core header was frozen for its C99 consumers
 EXT_SYMBOLS = ["ndfft_exec_weighted_device"]
+# ... ABI minor 5: ndfft_filter
+FILTER_SYMBOLS = ["ndfft_exec_filter_device"]
+FILTER_NO_FUSE = 1
 
 
 _loaded = []          # every Library this process has opened (tests/conftest.py reloads their switches between tests)
@@ -99,6 +102,11 @@ class Library:
         try:
             L.ndfft_exec_weighted_device.argtypes = [vp, i32, vp, vp, i32, i64p, i64p, i64p, i64p, i32, vp, sz, vp]; L.ndfft_exec_weighted_device.restype = i32
         except AttributeError:      # a side build older than ABI minor 4 (see above): Normalization.weights raises there
+            if not os.environ.get("NDFFT_MI355X_LIB"):
+                raise
+        try:
+            L.ndfft_exec_filter_device.argtypes = [vp, vp, vp, i32, i64p, i64p, i64p, i32, vp, sz, i32, dbl, i32, vp]; L.ndfft_exec_filter_device.restype = i32
+        except AttributeError:      # a side build older than ABI minor 5 (see above): ndfft_filter on device tensors raises there
             if not os.environ.get("NDFFT_MI355X_LIB"):
                 raise
 

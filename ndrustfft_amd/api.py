@@ -194,6 +194,70 @@ def nddct3(input, output, handler, axis): _transform(_lib.OP_DCT3, input, output
 def nddct4(input, output, handler, axis): _transform(_lib.OP_DCT4, input, output, handler, axis)
 
 
+def ndfft_filter(input, output, handler, axis, weights, *, fuse=True):
+    """output = IFFT(weights * FFT(input)) along `axis`, lane by lane: what ndfft -> `lane *= weights` -> ndifft give under the handler's normalisation (None:
+    unscaled, Default: 1 / n), in one call.  handler: an FftHandler (complex arrays, n weights) or an R2cFftHandler (real arrays, n // 2 + 1 complex weights;
+    meaning ndfft_r2c -> multiply -> ndifft_r2c).  `input is output` is the in-place filter.
+
+    torch tensors on the GPU go to ndfft_exec_filter_device (asynchronous on the current stream): one fused kernel for unit-stride power-of-two lanes of 64 .. 4096
+    points, transform + diagonal pass + transform otherwise (fuse=False forces that form).  `weights` is then a device tensor of the handler's complex dtype, or a
+    numpy array that is uploaded once per call.  numpy arrays run the three steps through the host calls."""
+    if not isinstance(handler, (FftHandler, R2cFftHandler)):
+        raise TypeError("handler must be an FftHandler or an R2cFftHandler")
+    if handler.norm.kind not in (Normalization.NONE, Normalization.DEFAULT):
+        raise ValueError("ndfft_filter: the handler's normalisation must be None or Default")
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or axis < 0:
+        raise TypeError("axis: usize")
+    r2c = isinstance(handler, R2cFftHandler)
+    cdt, adt = np.dtype(handler.complex_dtype), np.dtype(handler.real_dtype if r2c else handler.complex_dtype)
+    wlen = handler.n // 2 + 1 if r2c else handler.n
+    dev = _is_torch(input) or _is_torch(output)
+    if dev and not (_is_torch(input) and _is_torch(output) and input.is_cuda and output.is_cuda):
+        raise TypeError("device path needs both arrays as torch tensors on the GPU")
+    if _np_dtype_of(input) != adt or _np_dtype_of(output) != adt:
+        raise TypeError(f"element types must be {adt} -> {adt} for this handler")
+    if input.ndim != output.ndim:
+        raise TypeError("input and output must have the same dimensionality D")
+    if _np_dtype_of(weights) != cdt or weights.ndim != 1:
+        raise TypeError(f"weights: a vector of {cdt}")
+    if int(weights.shape[0]) != wlen:
+        raise ValueError(f"weights: got {int(weights.shape[0])} expected {wlen}")
+    L = handler._L
+    mode = _lib.NORM_NONE if handler.norm.kind == Normalization.NONE else _lib.NORM_DEFAULT
+    if not dev:
+        if _is_torch(weights):
+            raise TypeError("numpy arrays take numpy weights")
+        fwd, inv = (ndfft_r2c, ndifft_r2c) if r2c else (ndfft, ndifft)
+        sshape = [wlen if d == axis else int(s) for d, s in enumerate(input.shape)]
+        spec = np.zeros(sshape, cdt)
+        fwd(input, spec, handler, axis)
+        spec *= np.asarray(weights).reshape([wlen if d == axis else 1 for d in range(input.ndim)])
+        inv(spec, output, handler, axis)
+        return
+    if not hasattr(L.c, "ndfft_exec_filter_device"):
+        raise _lib.NdfftError(_lib.ERR_UNSUPPORTED, "this library build is older than ABI minor 5: no ndfft_exec_filter_device")
+    if input.device != output.device:
+        raise ValueError(f"input is on {input.device} but output is on {output.device}: both arrays must live on the same GPU")
+    if input is not output:
+        input = input.resolve_conj().resolve_neg()
+    if input.is_conj() or input.is_neg() or output.is_conj() or output.is_neg():
+        raise ValueError("a tensor written by the call has a lazy conj/neg bit set: pass a plain tensor (t.resolve_conj())")
+    if list(input.shape) != list(output.shape) and axis < input.ndim:
+        raise _lib.Panic(_lib.ERR_SHAPE_MISMATCH, f"ndfft_filter: input shape {tuple(input.shape)} differs from output shape {tuple(output.shape)}")
+    with torch.cuda.device(output.device):
+        if _is_torch(weights):
+            if weights.device != output.device:
+                raise ValueError("weights must live on the arrays' GPU")
+            wd = weights.resolve_conj().contiguous()
+        else:
+            wd = torch.from_numpy(np.ascontiguousarray(weights)).to(output.device)     # (stream-ordered: the caching allocator keeps it alive for the stream's work)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(output.device).cuda_stream)
+        st = L.c.ndfft_exec_filter_device(handler._plan, ctypes.c_void_p(input.data_ptr()), ctypes.c_void_p(output.data_ptr()), input.ndim,
+                                          _i64(list(input.shape)), _i64(list(input.stride())), _i64(list(output.stride())), int(axis),
+                                          ctypes.c_void_p(wd.data_ptr()), wlen, mode, 0.0, 0 if fuse else _lib.FILTER_NO_FUSE, stream)
+    L.check(st)
+
+
 # #[cfg(feature = "parallel")] twins (lib.rs:374-421, 589-611, 777-844).  On one GPU every lane is processed in
 # parallel anyway, so they are the same batched call; with set_par_devices([...]) they spread the call over several GPUs.
 def ndfft_par(input, output, handler, axis): _transform(_lib.OP_C2C_FWD, input, output, handler, axis, par=True)

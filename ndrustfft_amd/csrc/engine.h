@@ -133,7 +133,9 @@ struct DevConfig {                 // device copies (typed by dtype) of one FftC
     void *rfs_twlo = nullptr, *rfs_twhi = nullptr, *rfs_c1 = nullptr, *rfs_c2 = nullptr;
     void *wave_tw = nullptr;
     void *tinymat[4] = {nullptr, nullptr, nullptr, nullptr};
-    void *rader_bhat = nullptr, *rader_twp = nullptr, *rader_twp2 = nullptr, *rader_tab = nullptr, *twp_rev = nullptr, *rader_ctw = nullptr;   // ctw: W_mc^k of a two-factor cofactor
+    void *rader_bhat = nullptr, *rader_twp = nullptr, *rader_twp2 = nullptr, *rader_tab = nullptr, *twp_rev = nullptr, *rader_ctw = nullptr;
+    void *twp_filter = nullptr;    // C2C MAIN slot, pow2: twiddles of the reversed radix list for the fused filter (plan.hip: get_filter_twiddles; built and uploaded by the first filter call that needs them)
+    bool twp_filter_done = false;   // ctw: W_mc^k of a two-factor cofactor
 };
 
 enum ConfigSlot { CFG_MAIN = 0, CFG_DCT1 = 1, CFG_DCT4 = 2, CFG_COUNT = 3 };
@@ -183,6 +185,9 @@ const char *last_path();
 const std::string &last_err();
 void clear_err();
 int get_dev_tables(const ndfft_plan *plan, const DevTables **out);
+// the second pass set's twiddles of the fused filter on the CURRENT device: the plan's own table where the radix list is a palindrome, else a second table
+// built and uploaded at the first call (which therefore allocates; later calls do not)
+int get_filter_twiddles(const ndfft_plan *plan, const void **out);
 // host.hip: element range [lo, hi] (inclusive, relative to element 0) touched by a view -- also for shard.hip
 void view_range(int ndim, const int64_t *shape, const int64_t *stride, int64_t &lo, int64_t &hi, int64_t &count);
 
@@ -203,6 +208,15 @@ void pow2_build_twiddles(int dtype, int n, HostTable &out);
 int launch_pow2(int dtype, int n, const Pow2Args &a, hipStream_t s);
 int xcd_chunk_for(size_t block_bytes, int64_t nblk);   // lane blocks per XCD chunk of the workgroup -> lane map (0: identity)
 bool stream_loads_for(size_t in_bytes);                // input larger than the Infinity Cache: streaming (nt) loads
+// ... and the fused filter on the same lanes (filter_kernel.h): FFT, times w, inverse FFT in one launch
+struct FilterArgs {
+    Pow2Args a;              // in, out, nlanes, pitches, scale (of the inverse), twp (the plan's list), stream_in; `inverse` is not read
+    const void *twp_rev;     // per-pass twiddles of the reversed list (= twp for a palindromic list)
+    const void *w;           // n complex weights, indexed by output bin of the forward transform
+};
+bool filter_pow2_supported(int dtype, int n);
+void filter_pow2_build_twiddles(int dtype, int n, HostTable &out);   // twiddles of the reversed radix list (empty: the list is a palindrome, the plan's table serves)
+int launch_filter_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
 
 // kernels_wave.hip : LDS-free wavefront kernel (cross-lane shuffles) for dense C2C lanes of n = 2..64
 bool wave_supported(int n);

@@ -913,9 +913,10 @@ static Pow2Args c2c_row_args(const Call &k) {
     return a;
 }
 
-// tuned path: contiguous power-of-two C2C lanes at a uniform pitch
+// tuned path: contiguous power-of-two C2C lanes at a uniform pitch (the predicate is also the fused filter's: filter_fused)
+static bool pow2_rows_eligible(const Call &k) { return k.plan->kind == NDFFT_KIND_C2C && k.plan->cfg[CFG_MAIN].pow2 && k.L.rows; }
 static int route_pow2_rows(const Call &k) {
-    if (!(k.plan->kind == NDFFT_KIND_C2C && k.plan->cfg[CFG_MAIN].pow2 && k.L.rows)) return kDeclined;
+    if (!pow2_rows_eligible(k)) return kDeclined;
     Pow2Args a = c2c_row_args(k);
     if (k.L.dense) a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)k.P.nlanes * k.plan->n * 2 * real_size(k.plan->dtype));
     set_last_path("pow2_reg");
@@ -1226,6 +1227,98 @@ static int weighted_peeled(Problem &P, const char *d_in, char *d_out, size_t ein
     return NDFFT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// ndfft_filter (ndfft_exec_filter_device): out = s IFFT(w (.) FFT(in)) along the axis.  P is the FORWARD problem from the caller's input geometry to the caller's
+// OUTPUT geometry (sin / xs: input strides, sout / ys: output strides; for an R2C plan P.ylen is the half spectrum's length, the output lane has P.xlen reals).
+// ---------------------------------------------------------------------------------------------
+// fused: lanes on which dispatch() would run pow2_reg in both directions, n <= 4096 -- one launch, no scratch, no allocation after the first call of a plan whose
+// radix list is no palindrome (get_filter_twiddles)
+static int filter_fused(const Problem &P, const char *d_in, char *d_out, const void *d_w, hipStream_t stream) {
+    const DevTables *dt;
+    int rc = get_dev_tables(P.plan, &dt);
+    if (rc) return rc;
+    const Call k(P, d_in, d_out, stream, *dt);
+    if (!(pow2_rows_eligible(k) && filter_pow2_supported(k.plan->dtype, k.n))) return kDeclined;
+    FilterArgs f;
+    f.a = c2c_row_args(k);
+    f.w = d_w;
+    if ((rc = get_filter_twiddles(P.plan, &f.twp_rev))) return rc;
+    if (k.L.dense) f.a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)P.nlanes * k.plan->n * 2 * real_size(k.plan->dtype));
+    set_last_path("filter_pow2");
+    return launch_filter_pow2(k.plan->dtype, k.n, f, stream);
+}
+// adjacent batch dims that are contiguous in both views become one (as prepare() does)
+static void remerge(Problem &Q) {
+    std::vector<BatchDim> b;
+    for (const BatchDim &d : Q.b) {
+        if (!b.empty() && b.back().sin == d.shape * d.sin && b.back().sout == d.shape * d.sout) { b.back().shape *= d.shape; b.back().sin = d.sin; b.back().sout = d.sout; continue; }
+        b.push_back(d);
+    }
+    Q.b.swap(b);
+}
+// composed, one problem of <= kMaxBatchDims batch dims: forward dispatch() into a dense spectrum image S (in the input's own dimension order, as weighted() builds its
+// image, but with every dim materialised: the spectrum of a broadcast lane is written once per index), the diagonal pass in place on S (cache-allocating stores: the
+// inverse reads it at once), inverse dispatch() from S into the caller's output.  S is scratch slot 8, which no route's own scratch aliases.  Safe in place: the whole
+// input is in S before the inverse writes.
+static int filter_composed(const Problem &P, const char *d_in, char *d_out, const void *d_w, double scale, hipStream_t stream) {
+    const int dtype = P.plan->dtype;
+    const bool r2c = P.plan->kind == NDFFT_KIND_R2C;
+    const size_t ec = 2 * real_size(dtype);
+    const int nd = (int)P.b.size() + 1;            // index nd - 1: the axis
+    int order[kMaxBatchDims + 1];
+    auto stride_of = [&](int i) { return i == nd - 1 ? P.xs : P.b[i].sin; };
+    for (int i = 0; i < nd; ++i) order[i] = i;
+    std::stable_sort(order, order + nd, [&](int a, int b) {
+        const int64_t sa = std::llabs(stride_of(a)), sb = std::llabs(stride_of(b));
+        return sa != sb ? sa < sb : a > b;
+    });
+    Problem F = P, I = P;                          // F: caller's input -> S;  I: S -> caller's output
+    F.op = r2c ? NDFFT_OP_R2C : NDFFT_OP_C2C_FWD; F.scale = 1.0;
+    I.op = r2c ? NDFFT_OP_C2R : NDFFT_OP_C2C_INV; I.scale = scale; I.xlen = P.ylen; I.ylen = P.xlen;
+    int64_t run = 1;
+    for (int k = 0; k < nd; ++k) {
+        const int i = order[k];
+        if (i == nd - 1) { F.ys = I.xs = run; run *= P.ylen; }
+        else { F.b[i].sout = I.b[i].sin = run; run *= P.b[i].shape; }
+    }
+    remerge(F); remerge(I);
+    void *S;
+    int rc;
+    if ((rc = get_scratch(8, stream, (size_t)run * ec, &S))) return rc;
+    DeviceWs *ws;
+    if ((rc = current_ws(&ws))) return rc;
+    if ((rc = dispatch(F, d_in, S, stream))) return rc;
+    static thread_local std::string path;
+    const std::string fwd = last_path();
+    LaneGeom gs, unused;
+    lane_geoms(I, gs, unused);
+    if ((rc = launch_weights(S, S, d_w, gs, gs, P.ylen, dtype, 1, 0, stream))) return rc;
+    ws->mall.note_write(S, (size_t)run * ec);      // (speed only, as in weighted(): what a row kernel's load policy should expect of the image)
+    if ((rc = dispatch(I, S, d_out, stream))) return rc;
+    path = fwd + "+weights+" + last_path();
+    set_last_path(path.c_str());
+    return NDFFT_OK;
+}
+// more than kMaxBatchDims un-mergeable batch dims: peeled on the host like weighted_peeled
+static int filter_peeled(Problem &P, const char *d_in, char *d_out, size_t esz, const void *d_w, double scale, bool fuse, hipStream_t stream) {
+    if (P.b.size() <= (size_t)kMaxBatchDims) {
+        if (fuse) {
+            const int rc = filter_fused(P, d_in, d_out, d_w, stream);
+            if (rc != kDeclined) return rc;
+        }
+        return filter_composed(P, d_in, d_out, d_w, scale, stream);
+    }
+    BatchDim outer = P.b.front();
+    Problem Q = P;
+    Q.b.erase(Q.b.begin());
+    Q.nlanes = P.nlanes / outer.shape;
+    for (int64_t i = 0; i < outer.shape; ++i) {
+        int rc = filter_peeled(Q, d_in + i * outer.sin * (int64_t)esz, d_out + i * outer.sout * (int64_t)esz, esz, d_w, scale, fuse, stream);
+        if (rc) return rc;
+    }
+    return NDFFT_OK;
+}
+
 }  // namespace ndfft
 
 using namespace ndfft;
@@ -1269,6 +1362,38 @@ int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in,
         return fail(NDFFT_ERR_INVALID_ARG, m);
     }
     return weighted_peeled(P, (const char *)d_in, (char *)d_out, ein, eout, d_weights, (hipStream_t)stream);
+}
+
+int ndfft_exec_filter_device(const ndfft_plan *plan, const void *d_in, void *d_out, int ndim, const int64_t *shape, const int64_t *stride_in,
+                             const int64_t *stride_out, int axis, const void *d_weights, size_t n_weights, int norm, double scale, int flags, void *stream) {
+    clear_err();
+    g_last_policy = -1;
+    // the checks of ndfft_exec_device for the plan's forward op (a DCT plan has none here: "op does not belong to this plan's handler kind"); the forward op of an
+    // R2C plan maps the caller's real lane to a half spectrum, so its output extent along the axis is n / 2 + 1 whatever the caller's is
+    const bool r2c = plan && plan->kind == NDFFT_KIND_R2C;
+    int64_t shape_mid[NDFFT_MAX_DIMS];
+    const int64_t *shape_out = shape;
+    if (r2c && shape && ndim > 0 && ndim <= NDFFT_MAX_DIMS && axis >= 0 && axis < ndim) {
+        for (int d = 0; d < ndim; ++d) shape_mid[d] = shape[d];
+        shape_mid[axis] = (int64_t)plan->n / 2 + 1;
+        shape_out = shape_mid;
+    }
+    Problem P;
+    bool nothing;
+    int rc = prepare(plan, r2c ? NDFFT_OP_R2C : NDFFT_OP_C2C_FWD, ndim, shape, stride_in, shape_out, stride_out, axis, norm, scale, P, nothing);
+    if (rc || nothing) return rc;
+    if (!d_in || !d_out) return fail(NDFFT_ERR_INVALID_ARG, "null array pointer");
+    if (!d_weights) return fail(NDFFT_ERR_INVALID_ARG, "null weights pointer");
+    if ((int64_t)n_weights != P.ylen) {
+        char m[128];
+        snprintf(m, sizeof m, "weights: got %zu expected %lld (the length of the spectrum lane)", n_weights, (long long)P.ylen);
+        return fail(NDFFT_ERR_INVALID_ARG, m);
+    }
+    if (flags & ~NDFFT_FILTER_NO_FUSE) return fail(NDFFT_ERR_INVALID_ARG, "unknown filter flag");
+    const double s = norm == NDFFT_NORM_NONE ? 1.0 : norm == NDFFT_NORM_DEFAULT ? 1.0 / (double)plan->n : scale;
+    P.scale = s;                                   // (the fused kernel's; the composed route sets its two problems' own)
+    const size_t r = real_size(plan->dtype);
+    return filter_peeled(P, (const char *)d_in, (char *)d_out, r2c ? r : 2 * r, d_weights, s, !(flags & NDFFT_FILTER_NO_FUSE), (hipStream_t)stream);
 }
 
 int ndfft_last_input_policy(void) { return g_last_policy; }

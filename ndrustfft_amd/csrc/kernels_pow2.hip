@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "pow2_kernel.h"
+#include "filter_kernel.h"
 
 namespace ndfft {
 
@@ -194,6 +195,62 @@ int launch_pow2(int dtype, int n, const Pow2Args &a, hipStream_t s) {
         NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
 #undef NDFFT_CASE
         default: return fail(NDFFT_ERR_UNSUPPORTED, "pow2 kernel: unsupported n");
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// ndfft_filter, fused (filter_kernel.h): FFT, weights and inverse FFT of a lane in one launch.  n = 64 .. 4096; the two longest lengths (PSPLIT forms, 122-126
+// VGPRs for one pass set) stay on the composed route of exec.hip.  Same XCD map, load policy and 16-byte rule for f32 as launch_pow2 above.
+// ---------------------------------------------------------------------------------------------
+static constexpr int kFilterMaxN = 4096;
+bool filter_pow2_supported(int dtype, int n) { return n <= kFilterMaxN && pow2_supported(dtype, n); }
+// per-pass twiddles of the reversed radix list; empty when the list is a palindrome (the plan's own table serves both pass sets)
+void filter_pow2_build_twiddles(int dtype, int n, HostTable &out) {
+    switch (n) {
+#define NDFFT_CASE(N_, TPL_, ...)                                                                                                         \
+    case N_:                                                                                                                              \
+        if (dtype == NDFFT_F32) { if (!radix_palindromic<Pow2Cfg<float, N_>::RL>()) build_tw<Reversed<Pow2Cfg<float, N_>::RL>::type>(out); } \
+        else if (!radix_palindromic<Pow2Cfg<double, N_>::RL>()) build_tw<Reversed<Pow2Cfg<double, N_>::RL>::type>(out);                    \
+        break;
+        NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
+#undef NDFFT_CASE
+        default: break;
+    }
+}
+template <typename T, int N, int NT, int VEC> static int launch_filter_inst(const FilterArgs &f0, hipStream_t s) {
+    constexpr int TPL = Pow2Cfg<T, N>::TPL, LPB = lpb_for(TPL);
+    using K = FilterKernel<T, N, TPL, LPB, Pow2Half<T, N>::value, typename Pow2Cfg<T, N>::RL, N >= 4096 ? 16 : 0, NT, VEC>;
+    NDFFT_ENSURE_LDS_ATTR((k_filter_pow2<K>));
+    const int64_t nblk = (f0.a.nlanes + LPB - 1) / LPB;
+    if (nblk <= 0) return NDFFT_OK;
+    if (nblk > 0x7fffffffLL) return fail(NDFFT_ERR_UNSUPPORTED, "too many lanes for one launch");
+    FilterArgs f = f0;
+    f.a.xcd_chunk = xcd_chunk_for((size_t)LPB * N * sizeof(cpx<T>), nblk);
+    hipLaunchKernelGGL(k_filter_pow2<K>, dim3((unsigned)nblk), dim3(K::THREADS), K::LDS_BYTES, s, f);
+    NDFFT_HIP(hipGetLastError());
+    return NDFFT_OK;
+}
+template <typename T, int N, int VEC> static int launch_filter_one(const FilterArgs &f, hipStream_t s) {
+    const bool nt_in = f.a.stream_in >= 0 ? f.a.stream_in != 0 : stream_loads_for((size_t)f.a.nlanes * N * sizeof(cpx<T>));
+    return nt_in ? launch_filter_inst<T, N, 3, VEC>(f, s) : launch_filter_inst<T, N, 1, VEC>(f, s);
+}
+template <int N> static int launch_filter_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
+    if constexpr (N <= kFilterMaxN) {
+        if (dtype == NDFFT_F64) return launch_filter_one<double, N, 1>(f, s);
+        if constexpr (f32_can_vec2<N>()) { if (vec_ok) return launch_filter_one<float, N, 2>(f, s); }
+        return launch_filter_one<float, N, 1>(f, s);
+    } else {
+        return fail(NDFFT_ERR_UNSUPPORTED, "filter kernel: unsupported n");
+    }
+}
+int launch_filter_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s) {
+    const Pow2Args &a = f.a;
+    const bool vec_ok = a.pitch_in % 2 == 0 && a.pitch_out % 2 == 0 && ((uintptr_t)a.in % 16) == 0 && ((uintptr_t)a.out % 16) == 0;
+    switch (n) {
+#define NDFFT_CASE(N_, TPL_, ...) case N_: return launch_filter_n<N_>(dtype, vec_ok, f, s);
+        NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
+#undef NDFFT_CASE
+        default: return fail(NDFFT_ERR_UNSUPPORTED, "filter kernel: unsupported n");
     }
 }
 

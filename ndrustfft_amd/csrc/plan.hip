@@ -586,6 +586,23 @@ int get_dev_tables(const ndfft_plan *cplan, const DevTables **out) {
     return NDFFT_OK;
 }
 
+int get_filter_twiddles(const ndfft_plan *cplan, const void **out) {
+    const DevTables *dt;
+    int rc = get_dev_tables(cplan, &dt);
+    if (rc) return rc;
+    ndfft_plan *plan = const_cast<ndfft_plan *>(cplan);
+    std::lock_guard<std::mutex> g(plan->mu);
+    DevConfig &d = const_cast<DevConfig &>(dt->cfg[CFG_MAIN]);
+    if (!d.twp_filter_done) {
+        HostTable t;
+        filter_pow2_build_twiddles(plan->dtype, (int)plan->n, t);
+        if ((rc = upload_any(plan->dtype, t, &d.twp_filter))) return rc;
+        d.twp_filter_done = true;
+    }
+    *out = d.twp_filter ? d.twp_filter : d.twp;
+    return NDFFT_OK;
+}
+
 }  // namespace ndfft
 
 using namespace ndfft;
@@ -710,7 +727,7 @@ int ndfft_plan_destroy(ndfft_plan *plan) {
         (void)hipSetDevice(kv.first);
         for (int i = 0; i < CFG_COUNT; ++i) {
             DevConfig &d = kv.second.cfg[i];
-            void *ptrs[] = {d.tw, d.twM, d.chirp, d.bhat, d.aux1, d.aux2, d.twp, d.twlo, d.twhi, d.twp_col, d.twp_col_w, d.twp_fs, d.twp_jcol, d.twp_narrow, d.cs_twlo, d.cs_twhi, d.rfs_twlo, d.rfs_twhi, d.rfs_c1, d.rfs_c2, d.wave_tw, d.tinymat[0], d.tinymat[1], d.tinymat[2], d.tinymat[3], d.rader_bhat, d.rader_twp, d.rader_twp2, d.rader_tab, d.twp_rev, d.rader_ctw};
+            void *ptrs[] = {d.tw, d.twM, d.chirp, d.bhat, d.aux1, d.aux2, d.twp, d.twlo, d.twhi, d.twp_col, d.twp_col_w, d.twp_fs, d.twp_jcol, d.twp_narrow, d.cs_twlo, d.cs_twhi, d.rfs_twlo, d.rfs_twhi, d.rfs_c1, d.rfs_c2, d.wave_tw, d.tinymat[0], d.tinymat[1], d.tinymat[2], d.tinymat[3], d.rader_bhat, d.rader_twp, d.rader_twp2, d.rader_tab, d.twp_rev, d.rader_ctw, d.twp_filter};
             for (void *q : ptrs) if (q) (void)hipFree(q);
         }
     }

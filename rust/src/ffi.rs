@@ -30,6 +30,7 @@ pub const NDFFT_OP_DCT2: c_int = 5;
 pub const NDFFT_OP_DCT3: c_int = 6;
 pub const NDFFT_OP_DCT4: c_int = 7;
 
+pub const NDFFT_FILTER_NO_FUSE: c_int = 1;
 pub const NDFFT_NORM_NONE: c_int = 0;
 pub const NDFFT_NORM_DEFAULT: c_int = 1;
 
@@ -79,6 +80,14 @@ extern "C" {
         plan: *const ndfft_plan, op: c_int, d_input: *const c_void, d_output: *mut c_void, ndim: c_int,
         shape_in: *const i64, stride_in: *const i64, shape_out: *const i64, stride_out: *const i64,
         axis: c_int, d_weights: *const c_void, n_weights: usize, stream: *mut c_void,
+    ) -> c_int;
+    /// include/ndfft_mi355x_ext.h (ABI minor 5): out = s * IFFT(w (.) FFT(in)) along `axis` in one call -- C2C plan: complex arrays, n weights; R2C plan: real
+    /// arrays, n/2 + 1 complex weights.  One `shape`, a stride vector per array; `d_input == d_output` with equal strides is the in-place filter.
+    /// `flags`: NDFFT_FILTER_NO_FUSE takes the composed route even where the fused kernel exists
+    pub fn ndfft_exec_filter_device(
+        plan: *const ndfft_plan, d_input: *const c_void, d_output: *mut c_void, ndim: c_int,
+        shape: *const i64, stride_in: *const i64, stride_out: *const i64, axis: c_int,
+        d_weights: *const c_void, n_weights: usize, norm: c_int, scale: f64, flags: c_int, stream: *mut c_void,
     ) -> c_int;
     pub fn ndfft_dev_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn ndfft_dev_free(d_ptr: *mut c_void) -> c_int;

@@ -442,4 +442,35 @@ pub mod device {
     device_transform!(nddct2, T, T, DctHandler, ffi::NDFFT_OP_DCT2, before);
     device_transform!(nddct3, T, T, DctHandler, ffi::NDFFT_OP_DCT3, before);
     device_transform!(nddct4, T, T, DctHandler, ffi::NDFFT_OP_DCT4, before);
+
+    fn exec_filter_device<A: Copy, W: Copy>(plan: &Plan, input: &DeviceArray<A>, output: &mut DeviceArray<A>, axis: usize, weights: &DeviceArray<W>, mode: c_int, fuse: bool) {
+        check_axis(output.shape.len(), axis);
+        assert_eq!(input.shape, output.shape, "ndfft_filter: input and output shapes differ");
+        let (si, sti) = input.geom();
+        let (_, sto) = output.geom();
+        let nw: usize = weights.shape.iter().product();
+        check(unsafe {
+            ffi::ndfft_exec_filter_device(plan.0, input.ptr, output.ptr, si.len() as c_int, si.as_ptr(), sti.as_ptr(), sto.as_ptr(), axis as c_int,
+                                          weights.ptr, nw, mode, 0.0, if fuse { 0 } else { ffi::NDFFT_FILTER_NO_FUSE }, std::ptr::null_mut())
+        });
+    }
+    fn filter_mode<E>(norm: &Normalization<E>) -> c_int {
+        match norm {
+            Normalization::None => ffi::NDFFT_NORM_NONE,
+            Normalization::Default => ffi::NDFFT_NORM_DEFAULT,
+            _ => panic!("ndfft_filter: the handler's normalisation must be None or Default"),
+        }
+    }
+    /// `output = IFFT(weights * FFT(input))` along `axis`, lane by lane, in one call: what `ndfft`, a multiply of every lane by `weights` and `ndifft` give under the
+    /// handler's normalisation (None or Default).  Unit-stride power-of-two lanes of 64..=4096 points run one fused kernel, everything else transform + diagonal
+    /// pass + transform (`fuse = false` forces that form).  `weights`: `n` complex factors in device memory.
+    pub fn ndfft_filter<T: FftNum + FloatConst>(input: &DeviceArray<Complex<T>>, output: &mut DeviceArray<Complex<T>>, handler: &FftHandler<T>, axis: usize,
+                                                weights: &DeviceArray<Complex<T>>, fuse: bool) {
+        exec_filter_device(&handler.plan, input, output, axis, weights, filter_mode(&handler.norm), fuse);
+    }
+    /// The same on real arrays: `ndfft_r2c`, multiply by `n/2 + 1` complex factors, `ndifft_r2c`.
+    pub fn ndfft_filter_r2c<T: FftNum + FloatConst>(input: &DeviceArray<T>, output: &mut DeviceArray<T>, handler: &R2cFftHandler<T>, axis: usize,
+                                                    weights: &DeviceArray<Complex<T>>, fuse: bool) {
+        exec_filter_device(&handler.plan, input, output, axis, weights, filter_mode(&handler.norm), fuse);
+    }
 }

@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""What ndfft_filter costs on the MI355X (needs the GPU; fails without one).
+
+Device-resident arrays, HBM-sourced over rotating (in, out) pairs whose inputs add up to at least 768 MiB (three times the Infinity Cache), timed with device
+events after a warm-up that also ramps the clock.  For c128 and c64 and the shapes 4096 x 4096, 16384 x 1024 and 65536 x 256 (lanes along axis 1), in the same
+run, in alternating blocks:
+  two_calls   ndfft then ndifft through a work array: code the filter does not touch, and a lower bound for any three-call form (the multiply is left out)
+  composed    the filter with fuse=False: ndfft into the spectrum image, the diagonal pass in place, ndifft
+  fused       the filter's one kernel
+Reports the median block time per call in us and 2 x array bytes / time as a fraction of 8 TB/s.  One JSON line per configuration and a final line with all."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PEAK = 8e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=24, help="timed calls per block")
+    ap.add_argument("--blocks", type=int, default=5, help="alternating blocks per form")
+    ap.add_argument("--warmup", type=int, default=12)
+    ap.add_argument("--min-input-mib", type=int, default=768)
+    ap.add_argument("--shapes", default="4096x4096,16384x1024,65536x256")
+    ap.add_argument("--dtypes", default="c128,c64")
+    args = ap.parse_args()
+
+    import torch
+    assert torch.cuda.is_available(), "bench_filter.py needs an MI355X"
+    from ndrustfft_amd import FftHandler, _lib, ndfft, ndfft_filter, ndifft
+    L = _lib.default()
+    rng = np.random.default_rng(7)
+    results = []
+    for dname in args.dtypes.split(","):
+        cdt, rdt, rnp = (torch.complex128, torch.float64, np.float64) if dname == "c128" else (torch.complex64, torch.float32, np.float32)
+        for sh in args.shapes.split(","):
+            rows, n = (int(v) for v in sh.split("x"))
+            nbytes = rows * n * (16 if dname == "c128" else 8)
+            npairs = max(2, -(-(args.min_input_mib << 20) // nbytes))
+            h = FftHandler(n, rnp)
+            w = torch.from_numpy((rng.uniform(0.5, 2.0, n) * np.exp(2j * np.pi * rng.uniform(0, 1, n))).astype(np.complex128 if dname == "c128" else np.complex64)).to("cuda")
+            pairs = []
+            for _ in range(npairs):
+                x = torch.complex(torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5, torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5)
+                pairs.append((x, torch.zeros((rows, n), dtype=cdt, device="cuda"), torch.zeros((rows, n), dtype=cdt, device="cuda")))
+            k = [0]
+
+            def two_calls(x, y, work):
+                ndfft(x, work, h, 1); ndifft(work, y, h, 1)
+
+            def composed(x, y, work):
+                ndfft_filter(x, y, h, 1, w, fuse=False)
+
+            def fused(x, y, work):
+                ndfft_filter(x, y, h, 1, w)
+            forms = {"two_calls": two_calls, "composed": composed, "fused": fused}
+            routes = {}
+
+            def block(fn, steps):
+                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(steps):
+                    fn(*pairs[k[0] % npairs]); k[0] += 1
+                e1.record(); torch.cuda.synchronize()
+                return e0.elapsed_time(e1) * 1e3 / steps
+            for name, fn in forms.items():
+                for _ in range(args.warmup):
+                    fn(*pairs[k[0] % npairs]); k[0] += 1
+                torch.cuda.synchronize()
+                routes[name] = L.last_path()
+            times = {name: [] for name in forms}
+            for _ in range(args.blocks):
+                for name, fn in forms.items():
+                    times[name].append(block(fn, args.steps))
+            rec = {"dtype": dname, "shape": [rows, n], "pairs": npairs, "array_bytes": nbytes, "routes": routes}
+            for name in forms:
+                med = float(np.median(times[name]))
+                rec[name + "_us"] = round(med, 2); rec[name + "_us_blocks"] = [round(t, 2) for t in times[name]]
+                rec[name + "_frac_of_8TBps"] = round(2 * nbytes / (med * 1e-6) / PEAK, 3)
+            rec["fused_over_composed"] = round(rec["fused_us"] / rec["composed_us"], 3)
+            rec["fused_over_two_calls"] = round(rec["fused_us"] / rec["two_calls_us"], 3)
+            print(json.dumps(rec), flush=True)
+            results.append(rec)
+            del pairs
+            torch.cuda.empty_cache()
+    print(json.dumps({"bench_filter": results, "device": torch.cuda.get_device_name(0), "steps": args.steps, "blocks": args.blocks}))
+
+
+if __name__ == "__main__":
+    main()
