@@ -58,6 +58,11 @@ int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in,
  *                                      both arrays, lanes at a uniform pitch): ONE kernel, one read and one write of device memory per point, no scratch memory.
  *                                      Nothing is allocated except, at the first call of a plan whose radix list is no palindrome (f64 128, 1024, 2048; f32 2048), a
  *                                      second twiddle table: every other length can be captured into a HIP graph without a warm-up call.
+ *   "filter_r2c_pow2"                  R2C plan, n = 128 .. 8192 a power of two, unit stride along the axis in both arrays, lanes at a uniform pitch, both base
+ *                                      pointers multiples of 2 * sizeof(T) and both lane pitches even (every lane starts on a whole complex element): ONE kernel
+ *                                      on the real lane read as n / 2 complex points, one read and one write of device memory per real point, no scratch memory.
+ *                                      The first filter call of a plan builds and uploads the kernel's twiddle tables; later calls allocate nothing, so one
+ *                                      warm-up call is enough before a capture into a HIP graph.
  *   "<fwd route>+weights+<inv route>"  everything else, and every call with NDFFT_FILTER_NO_FUSE: forward transform into a dense spectrum image kept per host thread
  *                                      and stream, the diagonal pass in place on it, inverse transform into the output.  As for every multi-pass route the first call
  *                                      of a size allocates: warm a shape up before capturing it. */

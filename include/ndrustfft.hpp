@@ -489,9 +489,10 @@ NDRUSTFFT_DEFINE(nddct4, T, T, DctHandler, NDFFT_OP_DCT4, T, true, true)        
 
 // ---- ndfft_filter: output = IFFT(weights (.) FFT(input)) along `axis` in one call (ndfft_exec_filter_device, include/ndfft_mi355x_ext.h) --------------------
 // What ndfft -> `lane *= weights` -> ndifft (FftHandler; n complex weights) or ndfft_r2c -> multiply -> ndifft_r2c (R2cFftHandler; real arrays, n / 2 + 1 complex
-// weights) give under the handler's normalisation, which must be None or Default.  Unit-stride power-of-two lanes of 64 .. 4096 points run one fused kernel
-// (ndfft_last_path() == "filter_pow2"), everything else transform + diagonal pass + transform; fuse = false forces that form.  `&input == &output` is the in-place
-// filter.  Asynchronous on the default stream, like the other DeviceArray calls.
+// weights) give under the handler's normalisation, which must be None or Default.  Unit-stride power-of-two lanes run one fused kernel: complex lanes of
+// 64 .. 4096 points (ndfft_last_path() == "filter_pow2") and real lanes of 128 .. 8192 points that start on even element offsets ("filter_r2c_pow2"); everything
+// else runs transform + diagonal pass + transform, and fuse = false forces that form.  `&input == &output` is the in-place filter.
+// Asynchronous on the default stream, like the other DeviceArray calls.  Asynchronous on the default stream, like the other DeviceArray calls.
 namespace detail {
 template <typename A, typename T, typename NormT>
 void filter_device(const DeviceArray<A> &input, DeviceArray<A> &output, ndfft_plan *plan, const Normalization<NormT> &norm, std::size_t axis,

@@ -199,8 +199,9 @@ def ndfft_filter(input, output, handler, axis, weights, *, fuse=True):
     unscaled, Default: 1 / n), in one call.  handler: an FftHandler (complex arrays, n weights) or an R2cFftHandler (real arrays, n // 2 + 1 complex weights;
     meaning ndfft_r2c -> multiply -> ndifft_r2c).  `input is output` is the in-place filter.
 
-    torch tensors on the GPU go to ndfft_exec_filter_device (asynchronous on the current stream): one fused kernel for unit-stride power-of-two lanes of 64 .. 4096
-    points, transform + diagonal pass + transform otherwise (fuse=False forces that form).  `weights` is then a device tensor of the handler's complex dtype, or a
+    torch tensors on the GPU go to ndfft_exec_filter_device (asynchronous on the current stream): one fused kernel for unit-stride power-of-two lanes -- complex
+    lanes of 64 .. 4096 points (path "filter_pow2"), real lanes of 128 .. 8192 points that start on even element offsets ("filter_r2c_pow2") -- and transform +
+    diagonal pass + transform otherwise (fuse=False forces that form).  `weights` is then a device tensor of the handler's complex dtype, or a
     numpy array that is uploaded once per call.  numpy arrays run the three steps through the host calls."""
     if not isinstance(handler, (FftHandler, R2cFftHandler)):
         raise TypeError("handler must be an FftHandler or an R2cFftHandler")

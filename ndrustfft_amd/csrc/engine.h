@@ -136,6 +136,7 @@ struct DevConfig {                 // device copies (typed by dtype) of one FftC
     void *rader_bhat = nullptr, *rader_twp = nullptr, *rader_twp2 = nullptr, *rader_tab = nullptr, *twp_rev = nullptr, *rader_ctw = nullptr;
     void *twp_filter = nullptr;    // C2C MAIN slot, pow2: twiddles of the reversed radix list for the fused filter (plan.hip: get_filter_twiddles; built and uploaded by the first filter call that needs them)
     bool twp_filter_done = false;   // ctw: W_mc^k of a two-factor cofactor
+    void *twp_filter_fwd = nullptr;   // R2C MAIN slot: per-pass twiddles of the length-n/2 C2C list for the fused real filter (twp holds the real-op kernels' list); its reverse in twp_filter
 };
 
 enum ConfigSlot { CFG_MAIN = 0, CFG_DCT1 = 1, CFG_DCT4 = 2, CFG_COUNT = 3 };
@@ -188,6 +189,8 @@ int get_dev_tables(const ndfft_plan *plan, const DevTables **out);
 // the second pass set's twiddles of the fused filter on the CURRENT device: the plan's own table where the radix list is a palindrome, else a second table
 // built and uploaded at the first call (which therefore allocates; later calls do not)
 int get_filter_twiddles(const ndfft_plan *plan, const void **out);
+// the same for an R2C plan's fused real filter: both pass sets' twiddles of the length-n/2 C2C list (built and uploaded at the first call) and W_n^k (the plan's aux1)
+int get_filter_r2c_tables(const ndfft_plan *plan, const void **twp, const void **twp_rev, const void **wn);
 // host.hip: element range [lo, hi] (inclusive, relative to element 0) touched by a view -- also for shard.hip
 void view_range(int ndim, const int64_t *shape, const int64_t *stride, int64_t &lo, int64_t &hi, int64_t &count);
 
@@ -212,11 +215,16 @@ bool stream_loads_for(size_t in_bytes);                // input larger than the 
 struct FilterArgs {
     Pow2Args a;              // in, out, nlanes, pitches, scale (of the inverse), twp (the plan's list), stream_in; `inverse` is not read
     const void *twp_rev;     // per-pass twiddles of the reversed list (= twp for a palindromic list)
-    const void *w;           // n complex weights, indexed by output bin of the forward transform
+    const void *w;           // n complex weights, indexed by output bin of the forward transform (real lanes: n / 2 + 1)
+    const void *wn = nullptr;   // real lanes only: W_n^k, k = 0 .. n / 2 (the R2C plan's aux1)
 };
 bool filter_pow2_supported(int dtype, int n);
 void filter_pow2_build_twiddles(int dtype, int n, HostTable &out);   // twiddles of the reversed radix list (empty: the list is a palindrome, the plan's table serves)
 int launch_filter_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
+// ... and on real lanes of n points under an R2C plan (filter_kernel.h: REAL): the complex kernel of length n / 2; FilterArgs::a in COMPLEX elements
+bool filter_r2c_pow2_supported(int dtype, int n);
+void filter_r2c_build_twiddles(int dtype, int n, HostTable &fwd, HostTable &rev);   // per-pass twiddles of the length-n/2 list and of its reverse (empty: a palindrome)
+int launch_filter_r2c_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
 
 // kernels_wave.hip : LDS-free wavefront kernel (cross-lane shuffles) for dense C2C lanes of n = 2..64
 bool wave_supported(int n);

@@ -1232,12 +1232,28 @@ static int weighted_peeled(Problem &P, const char *d_in, char *d_out, size_t ein
 // OUTPUT geometry (sin / xs: input strides, sout / ys: output strides; for an R2C plan P.ylen is the half spectrum's length, the output lane has P.xlen reals).
 // ---------------------------------------------------------------------------------------------
 // fused: lanes on which dispatch() would run pow2_reg in both directions, n <= 4096 -- one launch, no scratch, no allocation after the first call of a plan whose
-// radix list is no palindrome (get_filter_twiddles)
+// radix list is no palindrome (get_filter_twiddles).  R2C plans: real lanes of n = 128 .. 8192 at unit stride and a uniform pitch, read as n / 2 complex points
+// (path filter_r2c_pow2) -- every lane base must then be a whole complex element: bases multiples of 2 sizeof(T), even pitches.  The first call of a plan builds
+// and uploads the tables of the length-n/2 list (get_filter_r2c_tables); later calls allocate nothing
 static int filter_fused(const Problem &P, const char *d_in, char *d_out, const void *d_w, hipStream_t stream) {
     const DevTables *dt;
     int rc = get_dev_tables(P.plan, &dt);
     if (rc) return rc;
     const Call k(P, d_in, d_out, stream, *dt);
+    if (k.plan->kind == NDFFT_KIND_R2C) {
+        const size_t r = real_size(k.plan->dtype);
+        const int64_t pin = P.b.empty() ? k.n : P.b[0].sin, pout = P.b.empty() ? k.n : P.b[0].sout;   // in reals (Layout's pitch_out is the half spectrum's without a batch dim)
+        if (!(k.L.rows && filter_r2c_pow2_supported(k.plan->dtype, k.n) && pin % 2 == 0 && pout % 2 == 0 && (uintptr_t)d_in % (2 * r) == 0 && (uintptr_t)d_out % (2 * r) == 0))
+            return kDeclined;
+        FilterArgs f;
+        f.a.in = d_in; f.a.out = d_out; f.a.nlanes = P.nlanes; f.a.pitch_in = pin / 2; f.a.pitch_out = pout / 2;
+        f.a.inverse = 0; f.a.scale = P.scale;
+        f.w = d_w;
+        if ((rc = get_filter_r2c_tables(P.plan, &f.a.twp, &f.twp_rev, &f.wn))) return rc;
+        if (pin == k.n && pout == k.n) f.a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)P.nlanes * k.plan->n * r);
+        set_last_path("filter_r2c_pow2");
+        return launch_filter_r2c_pow2(k.plan->dtype, k.n, f, stream);
+    }
     if (!(pow2_rows_eligible(k) && filter_pow2_supported(k.plan->dtype, k.n))) return kDeclined;
     FilterArgs f;
     f.a = c2c_row_args(k);

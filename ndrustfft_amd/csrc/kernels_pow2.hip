@@ -217,9 +217,9 @@ void filter_pow2_build_twiddles(int dtype, int n, HostTable &out) {
         default: break;
     }
 }
-template <typename T, int N, int NT, int VEC> static int launch_filter_inst(const FilterArgs &f0, hipStream_t s) {
+template <typename T, int N, int NT, int VEC, bool REAL = false> static int launch_filter_inst(const FilterArgs &f0, hipStream_t s) {
     constexpr int TPL = Pow2Cfg<T, N>::TPL, LPB = lpb_for(TPL);
-    using K = FilterKernel<T, N, TPL, LPB, Pow2Half<T, N>::value, typename Pow2Cfg<T, N>::RL, N >= 4096 ? 16 : 0, NT, VEC>;
+    using K = FilterKernel<T, N, TPL, LPB, Pow2Half<T, N>::value, typename Pow2Cfg<T, N>::RL, N >= 4096 ? 16 : 0, NT, VEC, REAL>;
     NDFFT_ENSURE_LDS_ATTR((k_filter_pow2<K>));
     const int64_t nblk = (f0.a.nlanes + LPB - 1) / LPB;
     if (nblk <= 0) return NDFFT_OK;
@@ -230,9 +230,9 @@ template <typename T, int N, int NT, int VEC> static int launch_filter_inst(cons
     NDFFT_HIP(hipGetLastError());
     return NDFFT_OK;
 }
-template <typename T, int N, int VEC> static int launch_filter_one(const FilterArgs &f, hipStream_t s) {
+template <typename T, int N, int VEC, bool REAL = false> static int launch_filter_one(const FilterArgs &f, hipStream_t s) {
     const bool nt_in = f.a.stream_in >= 0 ? f.a.stream_in != 0 : stream_loads_for((size_t)f.a.nlanes * N * sizeof(cpx<T>));
-    return nt_in ? launch_filter_inst<T, N, 3, VEC>(f, s) : launch_filter_inst<T, N, 1, VEC>(f, s);
+    return nt_in ? launch_filter_inst<T, N, 3, VEC, REAL>(f, s) : launch_filter_inst<T, N, 1, VEC, REAL>(f, s);
 }
 template <int N> static int launch_filter_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
     if constexpr (N <= kFilterMaxN) {
@@ -251,6 +251,44 @@ int launch_filter_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s) {
         NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
 #undef NDFFT_CASE
         default: return fail(NDFFT_ERR_UNSUPPORTED, "filter kernel: unsupported n");
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// ... and on REAL lanes of n = 2 F points under an R2C plan (filter_kernel.h: REAL): the complex kernel of length F with the mirror exchange and the pair mix between its
+// two pass sets.  F = 64 .. 4096, the lengths instantiated above, i.e. n = 128 .. 8192; kFilterR2cN is THE list of shipped instances (tests/filter_real_suite.py: FUSED_R_N
+// mirrors it): every one measured 53-67 % below the composed route.
+// The caller passes pitches in COMPLEX elements (half the real pitches) and bases that are whole complex elements.
+// ---------------------------------------------------------------------------------------------
+static constexpr int kFilterR2cN[] = {128, 256, 512, 1024, 2048, 4096, 8192};
+bool filter_r2c_pow2_supported(int dtype, int n) {
+    (void)dtype;
+    for (int m : kFilterR2cN) if (m == n) return filter_pow2_supported(dtype, n / 2);
+    return false;
+}
+// per-pass twiddles of the length-F list and of its reverse (empty: a palindrome), F = n / 2
+void filter_r2c_build_twiddles(int dtype, int n, HostTable &fwd, HostTable &rev) {
+    pow2_build_twiddles(dtype, n / 2, fwd);
+    filter_pow2_build_twiddles(dtype, n / 2, rev);
+}
+template <int N> static int launch_filter_r2c_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
+    if constexpr (N <= kFilterMaxN) {
+        if (dtype == NDFFT_F64) return launch_filter_one<double, N, 1, true>(f, s);
+        if constexpr (f32_can_vec2<N>()) { if (vec_ok) return launch_filter_one<float, N, 2, true>(f, s); }
+        return launch_filter_one<float, N, 1, true>(f, s);
+    } else {
+        return fail(NDFFT_ERR_UNSUPPORTED, "real filter kernel: unsupported n");
+    }
+}
+int launch_filter_r2c_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s) {
+    const Pow2Args &a = f.a;
+    if (!filter_r2c_pow2_supported(dtype, n)) return fail(NDFFT_ERR_UNSUPPORTED, "real filter kernel: unsupported n");
+    const bool vec_ok = a.pitch_in % 2 == 0 && a.pitch_out % 2 == 0 && ((uintptr_t)a.in % 16) == 0 && ((uintptr_t)a.out % 16) == 0;
+    switch (n / 2) {
+#define NDFFT_CASE(N_, TPL_, ...) case N_: return launch_filter_r2c_n<N_>(dtype, vec_ok, f, s);
+        NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
+#undef NDFFT_CASE
+        default: return fail(NDFFT_ERR_UNSUPPORTED, "real filter kernel: unsupported n");
     }
 }
 

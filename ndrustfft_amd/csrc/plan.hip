@@ -603,6 +603,26 @@ int get_filter_twiddles(const ndfft_plan *cplan, const void **out) {
     return NDFFT_OK;
 }
 
+int get_filter_r2c_tables(const ndfft_plan *cplan, const void **twp, const void **twp_rev, const void **wn) {
+    const DevTables *dt;
+    int rc = get_dev_tables(cplan, &dt);
+    if (rc) return rc;
+    ndfft_plan *plan = const_cast<ndfft_plan *>(cplan);
+    std::lock_guard<std::mutex> g(plan->mu);
+    DevConfig &d = const_cast<DevConfig &>(dt->cfg[CFG_MAIN]);
+    if (!d.twp_filter_done) {
+        HostTable fwd, rev;
+        filter_r2c_build_twiddles(plan->dtype, (int)plan->n, fwd, rev);
+        if (!d.twp_filter_fwd && (rc = upload_any(plan->dtype, fwd, &d.twp_filter_fwd))) return rc;
+        if ((rc = upload_any(plan->dtype, rev, &d.twp_filter))) return rc;
+        d.twp_filter_done = true;
+    }
+    *twp = d.twp_filter_fwd;
+    *twp_rev = d.twp_filter ? d.twp_filter : d.twp_filter_fwd;
+    *wn = d.aux1;
+    return NDFFT_OK;
+}
+
 }  // namespace ndfft
 
 using namespace ndfft;
@@ -727,7 +747,7 @@ int ndfft_plan_destroy(ndfft_plan *plan) {
         (void)hipSetDevice(kv.first);
         for (int i = 0; i < CFG_COUNT; ++i) {
             DevConfig &d = kv.second.cfg[i];
-            void *ptrs[] = {d.tw, d.twM, d.chirp, d.bhat, d.aux1, d.aux2, d.twp, d.twlo, d.twhi, d.twp_col, d.twp_col_w, d.twp_fs, d.twp_jcol, d.twp_narrow, d.cs_twlo, d.cs_twhi, d.rfs_twlo, d.rfs_twhi, d.rfs_c1, d.rfs_c2, d.wave_tw, d.tinymat[0], d.tinymat[1], d.tinymat[2], d.tinymat[3], d.rader_bhat, d.rader_twp, d.rader_twp2, d.rader_tab, d.twp_rev, d.rader_ctw, d.twp_filter};
+            void *ptrs[] = {d.tw, d.twM, d.chirp, d.bhat, d.aux1, d.aux2, d.twp, d.twlo, d.twhi, d.twp_col, d.twp_col_w, d.twp_fs, d.twp_jcol, d.twp_narrow, d.cs_twlo, d.cs_twhi, d.rfs_twlo, d.rfs_twhi, d.rfs_c1, d.rfs_c2, d.wave_tw, d.tinymat[0], d.tinymat[1], d.tinymat[2], d.tinymat[3], d.rader_bhat, d.rader_twp, d.rader_twp2, d.rader_tab, d.twp_rev, d.rader_ctw, d.twp_filter, d.twp_filter_fwd};
             for (void *q : ptrs) if (q) (void)hipFree(q);
         }
     }

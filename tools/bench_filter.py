@@ -2,10 +2,11 @@
 """What ndfft_filter costs on the MI355X (needs the GPU; fails without one).
 
 Device-resident arrays, HBM-sourced over rotating (in, out) pairs whose inputs add up to at least 768 MiB (three times the Infinity Cache), timed with device
-events after a warm-up that also ramps the clock.  For c128 and c64 and the shapes 4096 x 4096, 16384 x 1024 and 65536 x 256 (lanes along axis 1), in the same
-run, in alternating blocks:
-  two_calls   ndfft then ndifft through a work array: code the filter does not touch, and a lower bound for any three-call form (the multiply is left out)
-  composed    the filter with fuse=False: ndfft into the spectrum image, the diagonal pass in place, ndifft
+events after a warm-up that also ramps the clock.  For c128 and c64 (an FftHandler) or f64 and f32 (real arrays under an R2cFftHandler, n // 2 + 1 weights) and
+the shapes 4096 x 4096, 16384 x 1024 and 65536 x 256 (lanes along axis 1), in the same run, in alternating blocks:
+  two_calls   ndfft then ndifft (real: ndfft_r2c then ndifft_r2c) through a work array: code the filter does not touch, and a lower bound for any three-call
+              form (the multiply is left out)
+  composed    the filter with fuse=False: the forward transform into the spectrum image, the diagonal pass in place, the inverse
   fused       the filter's one kernel
 Reports the median block time per call in us and 2 x array bytes / time as a fraction of 8 TB/s.  One JSON line per configuration and a final line with all."""
 import argparse
@@ -27,31 +28,40 @@ def main():
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--min-input-mib", type=int, default=768)
     ap.add_argument("--shapes", default="4096x4096,16384x1024,65536x256")
-    ap.add_argument("--dtypes", default="c128,c64")
+    ap.add_argument("--dtypes", default="c128,c64", help="of c128, c64 (complex arrays) and f64, f32 (real arrays)")
     args = ap.parse_args()
 
     import torch
     assert torch.cuda.is_available(), "bench_filter.py needs an MI355X"
-    from ndrustfft_amd import FftHandler, _lib, ndfft, ndfft_filter, ndifft
+    from ndrustfft_amd import FftHandler, R2cFftHandler, _lib, ndfft, ndfft_filter, ndfft_r2c, ndifft, ndifft_r2c
     L = _lib.default()
     rng = np.random.default_rng(7)
     results = []
     for dname in args.dtypes.split(","):
-        cdt, rdt, rnp = (torch.complex128, torch.float64, np.float64) if dname == "c128" else (torch.complex64, torch.float32, np.float32)
+        assert dname in ("c128", "c64", "f64", "f32"), dname
+        real = dname[0] == "f"
+        cdt, rdt, rnp = (torch.complex128, torch.float64, np.float64) if dname in ("c128", "f64") else (torch.complex64, torch.float32, np.float32)
+        adt = rdt if real else cdt
         for sh in args.shapes.split(","):
             rows, n = (int(v) for v in sh.split("x"))
-            nbytes = rows * n * (16 if dname == "c128" else 8)
+            nbytes = rows * n * torch.empty((), dtype=adt).element_size()
             npairs = max(2, -(-(args.min_input_mib << 20) // nbytes))
-            h = FftHandler(n, rnp)
-            w = torch.from_numpy((rng.uniform(0.5, 2.0, n) * np.exp(2j * np.pi * rng.uniform(0, 1, n))).astype(np.complex128 if dname == "c128" else np.complex64)).to("cuda")
+            h = R2cFftHandler(n, rnp) if real else FftHandler(n, rnp)
+            m = n // 2 + 1 if real else n                           # the spectrum lane
+            w = torch.from_numpy((rng.uniform(0.5, 2.0, m) * np.exp(2j * np.pi * rng.uniform(0, 1, m))).astype(np.complex128 if rnp is np.float64 else np.complex64)).to("cuda")
             pairs = []
             for _ in range(npairs):
-                x = torch.complex(torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5, torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5)
-                pairs.append((x, torch.zeros((rows, n), dtype=cdt, device="cuda"), torch.zeros((rows, n), dtype=cdt, device="cuda")))
+                x = torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5
+                if not real:
+                    x = torch.complex(x, torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5)
+                pairs.append((x, torch.zeros((rows, n), dtype=adt, device="cuda"), torch.zeros((rows, m), dtype=cdt, device="cuda")))
             k = [0]
 
             def two_calls(x, y, work):
-                ndfft(x, work, h, 1); ndifft(work, y, h, 1)
+                if real:
+                    ndfft_r2c(x, work, h, 1); ndifft_r2c(work, y, h, 1)
+                else:
+                    ndfft(x, work, h, 1); ndifft(work, y, h, 1)
 
             def composed(x, y, work):
                 ndfft_filter(x, y, h, 1, w, fuse=False)
