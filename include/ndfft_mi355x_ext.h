@@ -1,6 +1,6 @@
 /*
  * ndfft_mi355x_ext.h -- entry points added to libndfft_mi355x.so after the core header was frozen for its C99 consumers
- * (ABI minor 4: the weighted call; minor 5: the filter).  C99; includes ndfft_mi355x.h.
+ * (ABI minor 4: the weighted call; minor 5: the filter; minor 6: the DCT filter).  C99; includes ndfft_mi355x.h.
  *
  * Normalization::Weights(w): a DIAGONAL normalisation -- a different factor per element of the lane (orthonormal DCT
  * scalings, DCT-I end-point factors, spectral filters, de-aliasing masks).  Unlike Normalization::Custom(fn), a host
@@ -46,7 +46,7 @@ int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in,
  *   C2C plan   in, out: Complex<T>, lane length n, one `shape`, a stride vector each;   d_weights: n x Complex<T>
  *   R2C plan   in, out: REAL T, lane length n; meaning ndfft_r2c -> *= w -> ndifft_r2c, so Im(DC) and, for even n, Im(Nyquist) of the product are dropped as
  *              C2R always drops them;                                                   d_weights: (n / 2 + 1) x Complex<T>
- *   DCT plan   NDFFT_ERR_INVALID_ARG
+ *   DCT plan   NDFFT_ERR_INVALID_ARG (the cosine pair has an entry point of its own: ndfft_exec_dct_filter_device below)
  *
  * Checks: those of ndfft_exec_device for the plan's forward op, with the same panic texts in the same order; then a NULL d_weights, then n_weights (the message
  * names both numbers), then unknown bits in `flags` (all NDFFT_ERR_INVALID_ARG).  A refused call launches nothing and writes nothing.
@@ -70,6 +70,30 @@ int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in,
 int ndfft_exec_filter_device(const ndfft_plan *plan, const void *d_in, void *d_out, int ndim,
                              const int64_t *shape, const int64_t *stride_in, const int64_t *stride_out, int axis,
                              const void *d_weights, size_t n_weights, int norm, double scale, int flags, void *stream);
+
+/* nddct_filter: for every lane along `axis`, out = s * DCT3(g (.) DCT2(in)) with the unnormalised lane definitions
+ *   C[k] = sum_j x[j] cos(pi (2j+1) k / (2n)),     y[j] = D[0] / 2 + sum_{k >= 1} D[k] cos(pi (2j+1) k / (2n))
+ * -- exactly what nddct2 -> lane *= g -> nddct3 give under the normalisation `norm`: s = 1 for NDFFT_NORM_NONE, 4 for NDFFT_NORM_DEFAULT (each of the two calls
+ * pre-scales its input by 2), `scale` for NDFFT_NORM_SCALE.  Unit weights return s * (n / 2) * in.  The building block of cosine / Chebyshev-basis solvers on the Gauss
+ * grid, Neumann-boundary Poisson and Helmholtz solves, de-aliasing and smoothing of non-periodic real data.
+ *
+ *   DCT plan   in, out: REAL T, lane length n, one `shape`, a stride vector each;   d_weights: n x T (REAL)
+ *   C2C plan, R2C plan   NDFFT_ERR_INVALID_ARG
+ *
+ * The argument list, `flags`, in-place rule and asynchrony are those of ndfft_exec_filter_device.  Checks: those of ndfft_exec_device for NDFFT_OP_DCT2, with the same
+ * panic texts in the same order ("Size mismatch in dct, got .. expected ..", the axis panic); then NULL array pointers, a NULL d_weights, n_weights != n (the message
+ * names both numbers), unknown bits in `flags` (all NDFFT_ERR_INVALID_ARG).  A refused call launches nothing and writes nothing.
+ *
+ * Routes (ndfft_last_path):
+ *   "filter_dct_pow2"                  n = 128 .. 8192 a power of two, unit stride along the axis in both arrays, lanes at a uniform pitch -- ANY base pointer and any
+ *                                      pitch (16-byte accesses where both sides allow them, element-wide ones otherwise): ONE kernel, one read and one write of
+ *                                      device memory per point, no scratch memory.  The first filter call of a plan builds and uploads the kernel's twiddle tables;
+ *                                      later calls allocate nothing, so one warm-up call is enough before a capture into a HIP graph.
+ *   "<dct2 route>+weights+<dct3 route>"  everything else, and every call with NDFFT_FILTER_NO_FUSE: DCT-II into a dense real image kept per host thread and stream, the
+ *                                      diagonal pass in place on it, DCT-III into the output; the first call of a size allocates. */
+int ndfft_exec_dct_filter_device(const ndfft_plan *plan, const void *d_in, void *d_out, int ndim,
+                                 const int64_t *shape, const int64_t *stride_in, const int64_t *stride_out, int axis,
+                                 const void *d_weights, size_t n_weights, int norm, double scale, int flags, void *stream);
 
 #ifdef __cplusplus
 }

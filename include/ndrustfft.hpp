@@ -520,6 +520,32 @@ void ndfft_filter(const DeviceArray<T> &input, DeviceArray<T> &output, const R2c
     detail::filter_device<T, T>(input, output, handler.plan(), handler.norm(), axis, weights, fuse);
 }
 
+// ---- nddct_filter: output = DCT3(weights (.) DCT2(input)) along `axis` in one call (ndfft_exec_dct_filter_device) ---------------------------------------------
+// What nddct2 -> `lane *= weights` -> nddct3 give under the handler's normalisation, None or Default (each of the two calls pre-scales by 2: 4 in all); n REAL
+// weights; unit weights return (n / 2) * input under None.  Unit-stride power-of-two lanes of 128 .. 8192 points at any offset and pitch run one fused kernel
+// (ndfft_last_path() == "filter_dct_pow2"); everything else runs nddct2 + diagonal pass + nddct3, and fuse = false forces that form.  `&input == &output` is the
+// in-place filter.
+namespace detail {
+template <typename T, typename NormT>
+void dct_filter_device(const DeviceArray<T> &input, DeviceArray<T> &output, ndfft_plan *plan, const Normalization<NormT> &norm, std::size_t axis,
+                       const DeviceArray<T> &weights, bool fuse) {
+    if (norm.kind != Normalization<NormT>::None && norm.kind != Normalization<NormT>::Default)
+        throw Error(NDFFT_ERR_INVALID_ARG, "nddct_filter: the handler's normalisation must be None or Default");
+    if (input.shape().size() != output.shape().size()) throw Error(NDFFT_ERR_INVALID_ARG, "input and output must have the same dimensionality D");
+    if (axis > 0x7fffffffu) throw Panic(NDFFT_ERR_AXIS, "index out of bounds");
+    if (axis < input.shape().size() && input.shape() != output.shape()) throw Panic(NDFFT_ERR_SHAPE_MISMATCH, "nddct_filter: input and output shapes differ");
+    std::size_t nw = 1;
+    for (auto e : weights.shape()) nw *= (std::size_t)e;
+    check(ndfft_exec_dct_filter_device(plan, input.ptr(), output.ptr(), (int)input.shape().size(), input.shape().data(), input.strides().data(),
+                                       output.strides().data(), (int)axis, weights.ptr(), nw,
+                                       norm.kind == Normalization<NormT>::Default ? NDFFT_NORM_DEFAULT : NDFFT_NORM_NONE, 0.0, fuse ? 0 : NDFFT_FILTER_NO_FUSE, nullptr));
+}
+}  // namespace detail
+template <typename T>
+void nddct_filter(const DeviceArray<T> &input, DeviceArray<T> &output, const DctHandler<T> &handler, std::size_t axis, const DeviceArray<T> &weights, bool fuse = true) {
+    detail::dct_filter_device<T>(input, output, handler.plan(), handler.norm(), axis, weights, fuse);
+}
+
 /// Selects the GPUs the `_par` functions spread one call over (ids as ndfft_set_device numbers them).
 inline void set_par_devices(std::vector<int> ids) { detail::par_devices_ref() = std::move(ids); }
 

@@ -32,6 +32,8 @@ EXT_SYMBOLS = ["ndfft_exec_weighted_device"]
 # ... ABI minor 5: ndfft_filter
 FILTER_SYMBOLS = ["ndfft_exec_filter_device"]
 FILTER_NO_FUSE = 1
+# ... ABI minor 6: nddct_filter
+DCT_FILTER_SYMBOLS = ["ndfft_exec_dct_filter_device"]
 
 
 _loaded = []          # every Library this process has opened (tests/conftest.py reloads their switches between tests)
@@ -107,6 +109,11 @@ class Library:
         try:
             L.ndfft_exec_filter_device.argtypes = [vp, vp, vp, i32, i64p, i64p, i64p, i32, vp, sz, i32, dbl, i32, vp]; L.ndfft_exec_filter_device.restype = i32
         except AttributeError:      # a side build older than ABI minor 5 (see above): ndfft_filter on device tensors raises there
+            if not os.environ.get("NDFFT_MI355X_LIB"):
+                raise
+        try:
+            L.ndfft_exec_dct_filter_device.argtypes = [vp, vp, vp, i32, i64p, i64p, i64p, i32, vp, sz, i32, dbl, i32, vp]; L.ndfft_exec_dct_filter_device.restype = i32
+        except AttributeError:      # a side build older than ABI minor 6 (see above): nddct_filter on device tensors raises there
             if not os.environ.get("NDFFT_MI355X_LIB"):
                 raise
 

@@ -259,6 +259,67 @@ def ndfft_filter(input, output, handler, axis, weights, *, fuse=True):
     L.check(st)
 
 
+def nddct_filter(input, output, handler, axis, weights, *, fuse=True):
+    """output = DCT3(weights * DCT2(input)) along `axis`, lane by lane: what nddct2 -> `lane *= weights` -> nddct3 give under the handler's normalisation (None:
+    unscaled, Default: each call pre-scales by 2, so 4 in all), in one call; unit weights return (n / 2) * input under None.  handler: a DctHandler; both arrays in
+    its real dtype; `weights`: n reals of that dtype.  `input is output` is the in-place filter.
+
+    torch tensors on the GPU go to ndfft_exec_dct_filter_device (asynchronous on the current stream): one fused kernel for unit-stride power-of-two lanes of
+    128 .. 8192 points at any offset and pitch (path "filter_dct_pow2"), and nddct2 + diagonal pass + nddct3 otherwise (fuse=False forces that form).  `weights` is
+    then a device tensor, or a numpy array that is uploaded once per call.  numpy arrays run the three steps through the host calls."""
+    if not isinstance(handler, DctHandler):
+        raise TypeError("handler must be a DctHandler")
+    if handler.norm.kind not in (Normalization.NONE, Normalization.DEFAULT):
+        raise ValueError("nddct_filter: the handler's normalisation must be None or Default")
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or axis < 0:
+        raise TypeError("axis: usize")
+    rdt = np.dtype(handler.real_dtype)
+    n = handler.n
+    dev = _is_torch(input) or _is_torch(output)
+    if dev and not (_is_torch(input) and _is_torch(output) and input.is_cuda and output.is_cuda):
+        raise TypeError("device path needs both arrays as torch tensors on the GPU")
+    if _np_dtype_of(input) != rdt or _np_dtype_of(output) != rdt:
+        raise TypeError(f"element types must be {rdt} -> {rdt} for this handler")
+    if input.ndim != output.ndim:
+        raise TypeError("input and output must have the same dimensionality D")
+    if _np_dtype_of(weights) != rdt or weights.ndim != 1:
+        raise TypeError(f"weights: a vector of {rdt}")
+    if int(weights.shape[0]) != n:
+        raise ValueError(f"weights: got {int(weights.shape[0])} expected {n}")
+    L = handler._L
+    mode = _lib.NORM_NONE if handler.norm.kind == Normalization.NONE else _lib.NORM_DEFAULT
+    if not dev:
+        if _is_torch(weights):
+            raise TypeError("numpy arrays take numpy weights")
+        coef = np.zeros([int(s) for s in input.shape], rdt)
+        nddct2(input, coef, handler, axis)
+        coef *= np.asarray(weights).reshape([n if d == axis else 1 for d in range(input.ndim)])
+        nddct3(coef, output, handler, axis)
+        return
+    if not hasattr(L.c, "ndfft_exec_dct_filter_device"):
+        raise _lib.NdfftError(_lib.ERR_UNSUPPORTED, "this library build is older than ABI minor 6: no ndfft_exec_dct_filter_device")
+    if input.device != output.device:
+        raise ValueError(f"input is on {input.device} but output is on {output.device}: both arrays must live on the same GPU")
+    if input is not output:
+        input = input.resolve_conj().resolve_neg()
+    if input.is_conj() or input.is_neg() or output.is_conj() or output.is_neg():
+        raise ValueError("a tensor written by the call has a lazy conj/neg bit set: pass a plain tensor (t.resolve_neg())")
+    if list(input.shape) != list(output.shape) and axis < input.ndim:
+        raise _lib.Panic(_lib.ERR_SHAPE_MISMATCH, f"nddct_filter: input shape {tuple(input.shape)} differs from output shape {tuple(output.shape)}")
+    with torch.cuda.device(output.device):
+        if _is_torch(weights):
+            if weights.device != output.device:
+                raise ValueError("weights must live on the arrays' GPU")
+            wd = weights.resolve_neg().contiguous()
+        else:
+            wd = torch.from_numpy(np.ascontiguousarray(weights)).to(output.device)     # (stream-ordered: the caching allocator keeps it alive for the stream's work)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(output.device).cuda_stream)
+        st = L.c.ndfft_exec_dct_filter_device(handler._plan, ctypes.c_void_p(input.data_ptr()), ctypes.c_void_p(output.data_ptr()), input.ndim,
+                                              _i64(list(input.shape)), _i64(list(input.stride())), _i64(list(output.stride())), int(axis),
+                                              ctypes.c_void_p(wd.data_ptr()), n, mode, 0.0, 0 if fuse else _lib.FILTER_NO_FUSE, stream)
+    L.check(st)
+
+
 # #[cfg(feature = "parallel")] twins (lib.rs:374-421, 589-611, 777-844).  On one GPU every lane is processed in
 # parallel anyway, so they are the same batched call; with set_par_devices([...]) they spread the call over several GPUs.
 def ndfft_par(input, output, handler, axis): _transform(_lib.OP_C2C_FWD, input, output, handler, axis, par=True)

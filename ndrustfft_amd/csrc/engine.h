@@ -136,7 +136,7 @@ struct DevConfig {                 // device copies (typed by dtype) of one FftC
     void *rader_bhat = nullptr, *rader_twp = nullptr, *rader_twp2 = nullptr, *rader_tab = nullptr, *twp_rev = nullptr, *rader_ctw = nullptr;
     void *twp_filter = nullptr;    // C2C MAIN slot, pow2: twiddles of the reversed radix list for the fused filter (plan.hip: get_filter_twiddles; built and uploaded by the first filter call that needs them)
     bool twp_filter_done = false;   // ctw: W_mc^k of a two-factor cofactor
-    void *twp_filter_fwd = nullptr;   // R2C MAIN slot: per-pass twiddles of the length-n/2 C2C list for the fused real filter (twp holds the real-op kernels' list); its reverse in twp_filter
+    void *twp_filter_fwd = nullptr;   // R2C and DCT MAIN slots: per-pass twiddles of the length-n/2 C2C list for the fused real / cosine filter (twp holds the real-op kernels' list); its reverse in twp_filter
 };
 
 enum ConfigSlot { CFG_MAIN = 0, CFG_DCT1 = 1, CFG_DCT4 = 2, CFG_COUNT = 3 };
@@ -190,7 +190,8 @@ int get_dev_tables(const ndfft_plan *plan, const DevTables **out);
 // built and uploaded at the first call (which therefore allocates; later calls do not)
 int get_filter_twiddles(const ndfft_plan *plan, const void **out);
 // the same for an R2C plan's fused real filter: both pass sets' twiddles of the length-n/2 C2C list (built and uploaded at the first call) and W_n^k (the plan's aux1)
-int get_filter_r2c_tables(const ndfft_plan *plan, const void **twp, const void **twp_rev, const void **wn);
+// A DCT plan's MAIN slot holds the same two tables for its fused filter (DCT-II, weights, DCT-III), built the same way; `c` then also receives e^{-i pi k/(2n)} (its aux2)
+int get_filter_r2c_tables(const ndfft_plan *plan, const void **twp, const void **twp_rev, const void **wn, const void **c = nullptr);
 // host.hip: element range [lo, hi] (inclusive, relative to element 0) touched by a view -- also for shard.hip
 void view_range(int ndim, const int64_t *shape, const int64_t *stride, int64_t &lo, int64_t &hi, int64_t &count);
 
@@ -217,6 +218,7 @@ struct FilterArgs {
     const void *twp_rev;     // per-pass twiddles of the reversed list (= twp for a palindromic list)
     const void *w;           // n complex weights, indexed by output bin of the forward transform (real lanes: n / 2 + 1)
     const void *wn = nullptr;   // real lanes only: W_n^k, k = 0 .. n / 2 (the R2C plan's aux1)
+    const void *c = nullptr;    // DCT lanes only: e^{-i pi k/(2n)}, k < n (the DCT plan's aux2); w is then n REAL weights
 };
 bool filter_pow2_supported(int dtype, int n);
 void filter_pow2_build_twiddles(int dtype, int n, HostTable &out);   // twiddles of the reversed radix list (empty: the list is a palindrome, the plan's table serves)
@@ -225,6 +227,9 @@ int launch_filter_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
 bool filter_r2c_pow2_supported(int dtype, int n);
 void filter_r2c_build_twiddles(int dtype, int n, HostTable &fwd, HostTable &rev);   // per-pass twiddles of the length-n/2 list and of its reverse (empty: a palindrome)
 int launch_filter_r2c_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
+// ... and on real lanes of n points under a DCT plan (filter_kernel.h: FILTER_DCT): out = s DCT3(g (.) DCT2(in)); FilterArgs::a in REAL elements, any base and pitch
+bool filter_dct_pow2_supported(int dtype, int n);
+int launch_filter_dct_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
 
 // kernels_wave.hip : LDS-free wavefront kernel (cross-lane shuffles) for dense C2C lanes of n = 2..64
 bool wave_supported(int n);

@@ -1234,12 +1234,24 @@ static int weighted_peeled(Problem &P, const char *d_in, char *d_out, size_t ein
 // fused: lanes on which dispatch() would run pow2_reg in both directions, n <= 4096 -- one launch, no scratch, no allocation after the first call of a plan whose
 // radix list is no palindrome (get_filter_twiddles).  R2C plans: real lanes of n = 128 .. 8192 at unit stride and a uniform pitch, read as n / 2 complex points
 // (path filter_r2c_pow2) -- every lane base must then be a whole complex element: bases multiples of 2 sizeof(T), even pitches.  The first call of a plan builds
-// and uploads the tables of the length-n/2 list (get_filter_r2c_tables); later calls allocate nothing
+// and uploads the tables of the length-n/2 list (get_filter_r2c_tables); later calls allocate nothing.  DCT plans (ndfft_exec_dct_filter_device): the same lanes and the
+// same tables plus the plan's aux2, path filter_dct_pow2, with NO alignment condition -- the kernel reads and writes the lane as reals
 static int filter_fused(const Problem &P, const char *d_in, char *d_out, const void *d_w, hipStream_t stream) {
     const DevTables *dt;
     int rc = get_dev_tables(P.plan, &dt);
     if (rc) return rc;
     const Call k(P, d_in, d_out, stream, *dt);
+    if (k.plan->kind == NDFFT_KIND_DCT) {
+        if (!(k.L.rows && filter_dct_pow2_supported(k.plan->dtype, k.n))) return kDeclined;
+        FilterArgs f;
+        f.a.in = d_in; f.a.out = d_out; f.a.nlanes = P.nlanes; f.a.pitch_in = k.L.pitch_in; f.a.pitch_out = k.L.pitch_out;   // in reals
+        f.a.inverse = 0; f.a.scale = P.scale;
+        f.w = d_w;
+        if ((rc = get_filter_r2c_tables(P.plan, &f.a.twp, &f.twp_rev, &f.wn, &f.c))) return rc;
+        if (k.L.dense) f.a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)P.nlanes * k.plan->n * real_size(k.plan->dtype));
+        set_last_path("filter_dct_pow2");
+        return launch_filter_dct_pow2(k.plan->dtype, k.n, f, stream);
+    }
     if (k.plan->kind == NDFFT_KIND_R2C) {
         const size_t r = real_size(k.plan->dtype);
         const int64_t pin = P.b.empty() ? k.n : P.b[0].sin, pout = P.b.empty() ? k.n : P.b[0].sout;   // in reals (Layout's pitch_out is the half spectrum's without a batch dim)
@@ -1275,11 +1287,12 @@ static void remerge(Problem &Q) {
 // composed, one problem of <= kMaxBatchDims batch dims: forward dispatch() into a dense spectrum image S (in the input's own dimension order, as weighted() builds its
 // image, but with every dim materialised: the spectrum of a broadcast lane is written once per index), the diagonal pass in place on S (cache-allocating stores: the
 // inverse reads it at once), inverse dispatch() from S into the caller's output.  S is scratch slot 8, which no route's own scratch aliases.  Safe in place: the whole
-// input is in S before the inverse writes.
+// input is in S before the inverse writes.  The two ops and the element of S come from the plan kind: C2C forward / inverse and R2C / C2R through a complex image with
+// complex weights, DCT-II / DCT-III through a REAL image with real weights (the diagonal pass in the form Normalization::Weights uses for the DCT ops).
 static int filter_composed(const Problem &P, const char *d_in, char *d_out, const void *d_w, double scale, hipStream_t stream) {
     const int dtype = P.plan->dtype;
-    const bool r2c = P.plan->kind == NDFFT_KIND_R2C;
-    const size_t ec = 2 * real_size(dtype);
+    const bool r2c = P.plan->kind == NDFFT_KIND_R2C, dct = P.plan->kind == NDFFT_KIND_DCT;
+    const size_t ec = (dct ? 1 : 2) * real_size(dtype);
     const int nd = (int)P.b.size() + 1;            // index nd - 1: the axis
     int order[kMaxBatchDims + 1];
     auto stride_of = [&](int i) { return i == nd - 1 ? P.xs : P.b[i].sin; };
@@ -1289,8 +1302,8 @@ static int filter_composed(const Problem &P, const char *d_in, char *d_out, cons
         return sa != sb ? sa < sb : a > b;
     });
     Problem F = P, I = P;                          // F: caller's input -> S;  I: S -> caller's output
-    F.op = r2c ? NDFFT_OP_R2C : NDFFT_OP_C2C_FWD; F.scale = 1.0;
-    I.op = r2c ? NDFFT_OP_C2R : NDFFT_OP_C2C_INV; I.scale = scale; I.xlen = P.ylen; I.ylen = P.xlen;
+    F.op = dct ? NDFFT_OP_DCT2 : r2c ? NDFFT_OP_R2C : NDFFT_OP_C2C_FWD; F.scale = 1.0;
+    I.op = dct ? NDFFT_OP_DCT3 : r2c ? NDFFT_OP_C2R : NDFFT_OP_C2C_INV; I.scale = scale; I.xlen = P.ylen; I.ylen = P.xlen;
     int64_t run = 1;
     for (int k = 0; k < nd; ++k) {
         const int i = order[k];
@@ -1308,7 +1321,7 @@ static int filter_composed(const Problem &P, const char *d_in, char *d_out, cons
     const std::string fwd = last_path();
     LaneGeom gs, unused;
     lane_geoms(I, gs, unused);
-    if ((rc = launch_weights(S, S, d_w, gs, gs, P.ylen, dtype, 1, 0, stream))) return rc;
+    if ((rc = launch_weights(S, S, d_w, gs, gs, P.ylen, dtype, dct ? 0 : 1, 0, stream))) return rc;
     ws->mall.note_write(S, (size_t)run * ec);      // (speed only, as in weighted(): what a row kernel's load policy should expect of the image)
     if ((rc = dispatch(I, S, d_out, stream))) return rc;
     path = fwd + "+weights+" + last_path();
@@ -1410,6 +1423,30 @@ int ndfft_exec_filter_device(const ndfft_plan *plan, const void *d_in, void *d_o
     P.scale = s;                                   // (the fused kernel's; the composed route sets its two problems' own)
     const size_t r = real_size(plan->dtype);
     return filter_peeled(P, (const char *)d_in, (char *)d_out, r2c ? r : 2 * r, d_weights, s, !(flags & NDFFT_FILTER_NO_FUSE), (hipStream_t)stream);
+}
+
+int ndfft_exec_dct_filter_device(const ndfft_plan *plan, const void *d_in, void *d_out, int ndim, const int64_t *shape, const int64_t *stride_in,
+                                 const int64_t *stride_out, int axis, const void *d_weights, size_t n_weights, int norm, double scale, int flags, void *stream) {
+    clear_err();
+    g_last_policy = -1;
+    // the checks of ndfft_exec_device for NDFFT_OP_DCT2 (a C2C or an R2C plan has no such op: "op does not belong to this plan's handler kind")
+    Problem P;
+    bool nothing;
+    int rc = prepare(plan, NDFFT_OP_DCT2, ndim, shape, stride_in, shape, stride_out, axis, norm, scale, P, nothing);
+    if (rc || nothing) return rc;
+    if (!d_in || !d_out) return fail(NDFFT_ERR_INVALID_ARG, "null array pointer");
+    if (!d_weights) return fail(NDFFT_ERR_INVALID_ARG, "null weights pointer");
+    if ((int64_t)n_weights != P.ylen) {
+        char m[128];
+        snprintf(m, sizeof m, "weights: got %zu expected %lld (the length of the coefficient lane)", n_weights, (long long)P.ylen);
+        return fail(NDFFT_ERR_INVALID_ARG, m);
+    }
+    if (flags & ~NDFFT_FILTER_NO_FUSE) return fail(NDFFT_ERR_INVALID_ARG, "unknown filter flag");
+    // nddct2 and nddct3 each pre-scale their input by 2 under Default (lib.rs:700-722, 736-741): both factors are exact, so the pair's is 4
+    const double s = norm == NDFFT_NORM_NONE ? 1.0 : norm == NDFFT_NORM_DEFAULT ? 4.0 : scale;
+    P.scale = s;                                   // (the fused kernel's; the composed route sets its two problems' own)
+    const size_t r = real_size(plan->dtype);
+    return filter_peeled(P, (const char *)d_in, (char *)d_out, r, d_weights, s, !(flags & NDFFT_FILTER_NO_FUSE), (hipStream_t)stream);
 }
 
 int ndfft_last_input_policy(void) { return g_last_policy; }

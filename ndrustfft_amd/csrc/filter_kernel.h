@@ -17,6 +17,20 @@
 //   Yk = w[k] X[k], Ym = w[N-k] X[N-k]  (k = 0: both lose their imaginary parts, as ndifft_r2c drops those of DC and Nyquist),   Z'[k] = (Yk + conj Ym) + i conj(W) (Yk - conj Ym)
 // The unnormalised inverse FFT_N of Z' is y[2m] + i y[2m+1] with y = n irfft(w (.) rfft(x)).  Both bins of a pair are computed by both threads that hold one of
 // them: twice the arithmetic of the split, no second exchange.
+//
+// FILTER_DCT: the same on a REAL lane of n = 2N points under a DCT plan (launch_filter_dct_pow2): out = s DCT3(g (.) DCT2(in)), g of n REAL values, both transforms the
+// unnormalised lane definitions C[k] = sum_j x[j] cos(pi (2j+1) k / (2n)),  y[j] = D[0] / 2 + sum_{k>=1} D[k] cos(pi (2j+1) k / (2n))  (Makhoul; realops.h G_DCT2_EVEN,
+// G_DCT3_EVEN).  With v[m] = x[2m], v[n-1-m] = x[2m+1] and V = RFFT_n(v), C[k] = Re(c_k V[k]), C[n-k] = -Im(c_k V[k]), c_k = e^{-i pi k/(2n)}; backwards
+// V'[k] = conj(c_k) (D[k] - i D[n-k]) / 2 (D[n] := 0), v' = n irfft(V'), y[2m] = v'[m], y[2m+1] = v'[n-1-m].  The kernel:
+//   load     the lane CONTIGUOUSLY (any base, any pitch: the accesses are sizeof(T) wide, or 16 bytes where the host found both sides aligned), through the lane's LDS
+//            into z[m] = v[2m] + i v[2m+1] = x[4m] + i x[4m+2] (m < N/2), x[2n-1-4m] + i x[2n-3-4m] (m >= N/2) in the registers jof<0> names.  Element j of the lane
+//            sits at slot(j): its class (j mod 4) block, position j / 4 -- both gathers then run at unit stride; where the exchange buffer holds one component (HALF)
+//            the even elements go through first (the z of m < N/2), then the odd ones
+//   mix      the real mode's exchange and split give V[k], V[N-k] (k = 0: V[0] and the Nyquist bin V[N]);  tk = c_k V[k], tm = c_{N-k} V[N-k];
+//            D[k] = g[k] Re tk, D[n-k] = -g[n-k] Im tk (k = 0: 0), D[N-k] = g[N-k] Re tm, D[N+k] = -g[N+k] Im tm (k = 0: D[N] again);
+//            V'[k], V'[N-k] as above, then herm_fold as in the real mode
+//   store    z' = y[4m] + i y[4m+2] / y[2n-1-4m] + i y[2n-3-4m]: the load's map backwards through the LDS, contiguous global stores.  Dead tail lanes take part in
+//            every staging barrier and store nothing; every load of a workgroup precedes its first barrier, so a call in place is safe.
 #pragma once
 #include "pow2_kernel.h"
 #include "realops.h"
@@ -46,23 +60,108 @@ template <typename T, int N> constexpr int filter_mix_split() {
     if (NDFFT_FILTER_MIX_SPLIT >= 0) return NDFFT_FILTER_MIX_SPLIT;
     return (sizeof(T) == 8 ? N >= 4096 : N >= 1024) ? 2 : 0;
 }
+// The thread index behind a wall the optimiser does not see through.  The staged load and the staged store of the DCT form compute the SAME LDS addresses from t, 4 E of
+// them; left alone the compiler computes them once and keeps them in registers across both pass sets (f64 F = 1024: 256 VGPRs + 7 AGPRs = one workgroup per CU; with
+// the index laundered in front of each stage 220 = two.  profiles/r12/kernel_resources_filter_dct.txt)
+__device__ __forceinline__ int opaque(int t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(t));
+#endif
+    return t;
+}
 __device__ __forceinline__ void mix_fence() {
 #if defined(__HIP_DEVICE_COMPILE__)
     __builtin_amdgcn_sched_barrier(0);
 #endif
 }
 
-template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS, int NT, int VEC, bool REAL = false> struct FilterKernel {
+// The DCT pair mix loads W, two c and four g per bin (the real one W and two w).  0: no fence; 8: a fence behind EVERY bin (the last radix is 8 throughout).  Per instance,
+// from the compiler's register counts (profiles/r12/kernel_resources_filter_dct.txt) and an A-B of two libraries built with NDFFT_FILTER_MIX_SPLIT = 0 / 8 on 2^24 points
+// (profiles/r12/bench_filter_dct_fence_none.jsonl, _fence_all.jsonl; us without -> with):
+//   f64  F = 64  71.9 -> 68.0 (120-140 -> 100-107 VGPRs),  F = 128  87.9 -> 75.2 (198 -> 165),  F = 512  87.8 -> 83.2 (140 -> 126),  F = 2048  124.4 -> 109.8 (same count)
+//   f32  F = 64  44.6 -> 41.9 (78-88 -> 66-71),  F = 256  55.4 -> 52.4;  F = 1024 and the 4-byte form of F = 2048 by count alone (186 -> 145, 180 -> 156; times within 2 %)
+// Every other instance is within 2 % either way and is left without, so that its loads overlap.
+template <typename T, int N, int VEC> constexpr int filter_mix_split_dct() {
+    if (NDFFT_FILTER_MIX_SPLIT >= 0) return NDFFT_FILTER_MIX_SPLIT;
+    if (sizeof(T) == 8) return N == 64 || N == 128 || N == 512 || N == 2048 ? 8 : 0;
+    return N == 64 || N == 256 || N == 1024 || (N == 2048 && VEC == 1) ? 8 : 0;
+}
+
+// MODE (a bool before the DCT form: false / true still name the first two)
+enum { FILTER_C2C = 0, FILTER_R2C = 1, FILTER_DCT = 2 };
+// FILTER_DCT: VEC is the number of REALS per global access (1, or 16 / sizeof(T)); the pass sets always own butterflies j = t + q TPL
+template <typename T, int V> struct real_vec { typedef T type __attribute__((ext_vector_type(V))); };
+
+template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS, int NT, int VEC, int MODE = FILTER_C2C> struct FilterKernel {
+    static constexpr bool REAL = MODE == FILTER_R2C, DCT = MODE == FILTER_DCT, MIRROR = REAL || DCT;
     using RLR = typename Reversed<RL>::type;
-    using KF = Pow2Kernel<T, N, TPL, LPB, HALF, RL, FLAGS, 1, NT, VEC>;
-    using KI = Pow2Kernel<T, N, TPL, LPB, HALF, RLR, FLAGS, 1, NT, VEC>;
-    static constexpr int E = KF::E, THREADS = KF::THREADS, NP = RL::NP, MIX_SPLIT = filter_mix_split<T, N>();
+    using KF = Pow2Kernel<T, N, TPL, LPB, HALF, RL, FLAGS, 1, NT, DCT ? 1 : VEC>;
+    using KI = Pow2Kernel<T, N, TPL, LPB, HALF, RLR, FLAGS, 1, NT, DCT ? 1 : VEC>;
+    static constexpr int E = KF::E, THREADS = KF::THREADS, NP = RL::NP, MIX_SPLIT = DCT ? filter_mix_split_dct<T, N, VEC>() : filter_mix_split<T, N>();
     static constexpr size_t LDS_BYTES = KF::LDS_BYTES;
     static constexpr int R0 = RL::at(0), NB0 = N / R0, NBF0 = KF::slots(0);                  // first pass of the forward list = last pass of the reversed one
     static constexpr int RZ = RL::at(NP - 1), NBZ = N / RZ, NBFZ = KF::slots(NP - 1);        // last pass of the forward list = first pass of the reversed one
     static_assert(KI::E == E && E * TPL == N, "both lists run whole butterfly rounds on the same registers");
     static_assert(KF::full(0) && KF::full(NP - 1), "whole rounds in the first and last pass");
-    static_assert(VEC == 1 || (NBF0 % 2 == 0 && NBFZ % 2 == 0), "VEC = 2 needs an even number of butterfly rounds in the first and last pass");
+    static_assert(DCT || VEC == 1 || (NBF0 % 2 == 0 && NBFZ % 2 == 0), "VEC = 2 needs an even number of butterfly rounds in the first and last pass");
+    static_assert(MIX_SPLIT == 0 || RZ % MIX_SPLIT == 0, "a fence behind every RZ / MIX_SPLIT bins");
+    static_assert(!DCT || (R0 % 2 == 0 && (2 * E) % VEC == 0 && N % 4 == 0 && (VEC == 1 || VEC * sizeof(T) == 16)), "DCT: whole accesses per thread; r < R0 / 2 names the z of m < N / 2");
+
+    // FILTER_DCT staging.  Register x[i VEC + e] of thread t is element xj(t, i, e) of the lane: access i of a thread is the VEC reals from (t + i TPL) VEC on
+    static constexpr int NX = 2 * E, NA = NX / VEC, ROUNDS = HALF ? 2 : 1, ODD0 = HALF ? 0 : N;
+    static __device__ __forceinline__ int xj(int t, int i, int e) { return (t + i * TPL) * VEC + e; }
+    // where element j waits in the lane's LDS, in reals: [odd j: a second half of the buffer, unless the odd elements have a round of their own] [bit 1 of j: N / 2] [j / 4]
+    static __device__ __forceinline__ int slot(int j) { return phi((HALF ? 0 : (j & 1) * N) + ((j >> 1) & 1) * (N / 2) + (j >> 2)); }
+    // z[m] <-> (lane elements, as slots): m < N / 2: x[4m], x[4m+2];  m >= N / 2, p = N - 1 - m: x[4p+3], x[4p+1]
+    static __device__ __forceinline__ void stage_in(const T (&x)[NX], cpx<T> (&v)[E], char *lds, int t0) {
+        T *s = (T *)lds;
+        const int t = opaque(t0);
+#pragma unroll
+        for (int h = 0; h < ROUNDS; ++h) {
+            if (h) __syncthreads();            // the first round's gathers are done
+#pragma unroll
+            for (int i = 0; i < NA; ++i)
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const int j = xj(t, i, e);
+                    if (!HALF || (j & 1) == h) s[slot(j)] = x[i * VEC + e];
+                }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < NBF0; ++q)
+#pragma unroll
+                for (int r = 0; r < R0; ++r) {
+                    const int m = KF::template jof<0>(t, q) + r * NB0, p = N - 1 - m;
+                    if (r < R0 / 2) { if (!HALF || h == 0) v[q * R0 + r] = mk<T>(s[phi(m)], s[phi(N / 2 + m)]); }
+                    else if (!HALF || h == 1) v[q * R0 + r] = mk<T>(s[phi(ODD0 + N / 2 + p)], s[phi(ODD0 + p)]);
+                }
+        }
+    }
+    static __device__ __forceinline__ void stage_out(const cpx<T> (&v)[E], T (&x)[NX], char *lds, int t0) {
+        T *s = (T *)lds;
+        const int t = opaque(t0);
+#pragma unroll
+        for (int h = 0; h < ROUNDS; ++h) {
+            __syncthreads();                   // no thread still gathers from the second pass set's last exchange, or from the first round
+#pragma unroll
+            for (int q = 0; q < NBF0; ++q)
+#pragma unroll
+                for (int r = 0; r < R0; ++r) {
+                    const int m = KI::template jof<NP - 1>(t, q) + r * NB0, p = N - 1 - m;
+                    const cpx<T> z = v[q * R0 + r];
+                    if (r < R0 / 2) { if (!HALF || h == 0) { s[phi(m)] = z.x; s[phi(N / 2 + m)] = z.y; } }
+                    else if (!HALF || h == 1) { s[phi(ODD0 + N / 2 + p)] = z.x; s[phi(ODD0 + p)] = z.y; }
+                }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < NA; ++i)
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const int j = xj(t, i, e);
+                    if (!HALF || (j & 1) == h) x[i * VEC + e] = s[slot(j)];
+                }
+        }
+    }
     static_assert((FLAGS & ~16) == 0, "product flags other than the derived twiddle powers have no meaning here");
 
     static __device__ __forceinline__ void run(const FilterArgs &f) {
@@ -75,7 +174,23 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
         cpx<T> *out = (cpx<T> *)a.out + (live ? lane : 0) * a.pitch_out;
         char *lds = smem + (size_t)ll * KF::LANE_LDS * (HALF ? sizeof(T) : 2 * sizeof(T));
         cpx<T> v[E];
-        if constexpr (VEC == 2) {
+        if constexpr (DCT) {
+            const T *xin = (const T *)a.in + (live ? lane : 0) * a.pitch_in;      // (pitches in reals)
+            T x[NX];
+#pragma unroll
+            for (int i = 0; i < NA; ++i) {
+                if constexpr (VEC == 1) {
+                    if constexpr ((NT & 2) != 0) x[i] = __builtin_nontemporal_load(xin + xj(t, i, 0)); else x[i] = xin[xj(t, i, 0)];
+                } else {
+                    typedef typename real_vec<T, VEC>::type XV;
+                    XV w;
+                    if constexpr ((NT & 2) != 0) w = __builtin_nontemporal_load((const XV *)(xin + xj(t, i, 0))); else w = *(const XV *)(xin + xj(t, i, 0));
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) x[i * VEC + e] = w[e];
+                }
+            }
+            stage_in(x, v, lds, t);
+        } else if constexpr (VEC == 2) {
 #pragma unroll
             for (int q = 0; q < NBF0; q += 2)
 #pragma unroll
@@ -91,7 +206,7 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
         }
         KF::template passes<0>(v, (const cpx<T> *)a.twp, lds, t);
         // v[q RZ + r] is bin jof<NP-1>(t, q) + r NBZ: times its weight (default cache policy: every lane reads the same vector), conjugated for the inverse
-        if constexpr (!REAL) {
+        if constexpr (!MIRROR) {
             const cpx<T> *w = (const cpx<T> *)f.w;
 #pragma unroll
             for (int q = 0; q < NBFZ; ++q)
@@ -132,6 +247,27 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
 #pragma unroll
                     for (int r = 0; r < RZ; ++r) b[q * RZ + r] = s[phi((N - (KF::template jof<NP - 1>(t, q) + r * NBZ)) & (N - 1))];
             }
+            if constexpr (DCT) {
+                // pair mix (the formulas at the top).  g: 2 N reals, c[k] = e^{-i pi k/(4N)}, k < 2 N, wn[k] = W_n^k, k <= N: default cache policy, every lane reads the same
+                const T *g = (const T *)f.w;
+                const cpx<T> *wn = (const cpx<T> *)f.wn, *c = (const cpx<T> *)f.c;
+                const T hf = (T)0.5;
+#pragma unroll
+                for (int q = 0; q < NBFZ; ++q)
+#pragma unroll
+                    for (int r = 0; r < RZ; ++r) {
+                        const int k = KF::template jof<NP - 1>(t, q) + r * NBZ;
+                        const cpx<T> A = v[q * RZ + r], B = cconj(b[q * RZ + r]), W = wn[k], ck = c[k], cm = c[N - k];
+                        const cpx<T> e = mk<T>((A.x + B.x) * hf, (A.y + B.y) * hf);
+                        const cpx<T> o = cmul(mk<T>((A.y - B.y) * hf, -(A.x - B.x) * hf), W);
+                        const cpx<T> tk = cmul(ck, cadd(e, o)), tm = cmul(cm, cconj(csub(e, o)));                  // c_k V[k], c_{N-k} V[N-k]
+                        const T dk = hf * g[k] * tk.x, dm = hf * g[N - k] * tm.x;                                    // D[k] / 2, D[N-k] / 2
+                        const T dnk = k ? -hf * g[(2 * N - k) & (2 * N - 1)] * tk.y : (T)0, dpk = k ? -hf * g[N + k] * tm.y : dm;     // D[n-k] / 2 (D[n] := 0; g has no element n), D[N+k] / 2 (k = 0: D[N] once)
+                        const cpx<T> vk = cmul(cconj(ck), mk<T>(dk, -dnk)), vm = cmul(cconj(cm), mk<T>(dm, -dpk));   // V'[k], V'[N-k]
+                        v[q * RZ + r] = herm_fold<T>(vk, cconj(vm), W);      // conj(Z'[k]): the inverse runs forward passes
+                        if constexpr (MIX_SPLIT > 0) { if ((r + 1) % (RZ / MIX_SPLIT) == 0) mix_fence(); }
+                    }
+            } else {
             // pair mix (the formulas at the top; r2c_split_pair and herm_fold of realops.h on registers).  w: N + 1 values, default cache policy; wn[k] = W_n^k, k <= N
             const cpx<T> *w = (const cpx<T> *)f.w, *wn = (const cpx<T> *)f.wn;
 #pragma unroll
@@ -147,14 +283,32 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
                     v[q * RZ + r] = herm_fold<T>(yk, cconj(ym), W);      // conj(Z'[k]): the inverse runs forward passes
                     if constexpr (MIX_SPLIT > 0) { if ((r + 1) % (RZ / MIX_SPLIT) == 0) mix_fence(); }
                 }
+            }
         }
         // (the first exchange of the second pass set starts with a barrier: no thread overwrites LDS another still reads from the first set's last exchange, or gathers from)
         KI::template passes<0>(v, (const cpx<T> *)f.twp_rev, lds, t);
-        if (!live) return;
+        if constexpr (!DCT) { if (!live) return; }
         const T sc = (T)a.scale;
 #pragma unroll
         for (int i = 0; i < E; ++i) { v[i].x *= sc; v[i].y *= -sc; }
-        if constexpr (VEC == 2) {
+        if constexpr (DCT) {
+            T x[NX];
+            stage_out(v, x, lds, t);
+            if (!live) return;
+            T *xout = (T *)a.out + lane * a.pitch_out;
+#pragma unroll
+            for (int i = 0; i < NA; ++i) {
+                if constexpr (VEC == 1) {
+                    if constexpr ((NT & 1) != 0) __builtin_nontemporal_store(x[i], xout + xj(t, i, 0)); else xout[xj(t, i, 0)] = x[i];
+                } else {
+                    typedef typename real_vec<T, VEC>::type XV;
+                    XV w;
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) w[e] = x[i * VEC + e];
+                    if constexpr ((NT & 1) != 0) __builtin_nontemporal_store(w, (XV *)(xout + xj(t, i, 0))); else *(XV *)(xout + xj(t, i, 0)) = w;
+                }
+            }
+        } else if constexpr (VEC == 2) {
 #pragma unroll
             for (int q = 0; q < NBF0; q += 2)
 #pragma unroll

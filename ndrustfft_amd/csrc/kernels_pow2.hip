@@ -217,9 +217,9 @@ void filter_pow2_build_twiddles(int dtype, int n, HostTable &out) {
         default: break;
     }
 }
-template <typename T, int N, int NT, int VEC, bool REAL = false> static int launch_filter_inst(const FilterArgs &f0, hipStream_t s) {
+template <typename T, int N, int NT, int VEC, int MODE = FILTER_C2C> static int launch_filter_inst(const FilterArgs &f0, hipStream_t s) {
     constexpr int TPL = Pow2Cfg<T, N>::TPL, LPB = lpb_for(TPL);
-    using K = FilterKernel<T, N, TPL, LPB, Pow2Half<T, N>::value, typename Pow2Cfg<T, N>::RL, N >= 4096 ? 16 : 0, NT, VEC, REAL>;
+    using K = FilterKernel<T, N, TPL, LPB, Pow2Half<T, N>::value, typename Pow2Cfg<T, N>::RL, N >= 4096 ? 16 : 0, NT, VEC, MODE>;
     NDFFT_ENSURE_LDS_ATTR((k_filter_pow2<K>));
     const int64_t nblk = (f0.a.nlanes + LPB - 1) / LPB;
     if (nblk <= 0) return NDFFT_OK;
@@ -230,9 +230,9 @@ template <typename T, int N, int NT, int VEC, bool REAL = false> static int laun
     NDFFT_HIP(hipGetLastError());
     return NDFFT_OK;
 }
-template <typename T, int N, int VEC, bool REAL = false> static int launch_filter_one(const FilterArgs &f, hipStream_t s) {
+template <typename T, int N, int VEC, int MODE = FILTER_C2C> static int launch_filter_one(const FilterArgs &f, hipStream_t s) {
     const bool nt_in = f.a.stream_in >= 0 ? f.a.stream_in != 0 : stream_loads_for((size_t)f.a.nlanes * N * sizeof(cpx<T>));
-    return nt_in ? launch_filter_inst<T, N, 3, VEC, REAL>(f, s) : launch_filter_inst<T, N, 1, VEC, REAL>(f, s);
+    return nt_in ? launch_filter_inst<T, N, 3, VEC, MODE>(f, s) : launch_filter_inst<T, N, 1, VEC, MODE>(f, s);
 }
 template <int N> static int launch_filter_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
     if constexpr (N <= kFilterMaxN) {
@@ -273,9 +273,9 @@ void filter_r2c_build_twiddles(int dtype, int n, HostTable &fwd, HostTable &rev)
 }
 template <int N> static int launch_filter_r2c_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
     if constexpr (N <= kFilterMaxN) {
-        if (dtype == NDFFT_F64) return launch_filter_one<double, N, 1, true>(f, s);
-        if constexpr (f32_can_vec2<N>()) { if (vec_ok) return launch_filter_one<float, N, 2, true>(f, s); }
-        return launch_filter_one<float, N, 1, true>(f, s);
+        if (dtype == NDFFT_F64) return launch_filter_one<double, N, 1, FILTER_R2C>(f, s);
+        if constexpr (f32_can_vec2<N>()) { if (vec_ok) return launch_filter_one<float, N, 2, FILTER_R2C>(f, s); }
+        return launch_filter_one<float, N, 1, FILTER_R2C>(f, s);
     } else {
         return fail(NDFFT_ERR_UNSUPPORTED, "real filter kernel: unsupported n");
     }
@@ -289,6 +289,37 @@ int launch_filter_r2c_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s)
         NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
 #undef NDFFT_CASE
         default: return fail(NDFFT_ERR_UNSUPPORTED, "real filter kernel: unsupported n");
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// ... and on REAL lanes of n = 2 F points under a DCT plan (filter_kernel.h: FILTER_DCT): DCT-II, n real weights, DCT-III.  The same complex kernel of length F between a
+// staged load through Makhoul's permutation and a staged store through its inverse.  kFilterDctN is THE list of shipped instances (tests/filter_dct_suite.py: FUSED_D_N
+// mirrors it).  Pitches in REALS; any base and any pitch: the accesses are sizeof(T) wide unless both sides are 16-byte aligned (bases and pitches), then 16 bytes.
+// ---------------------------------------------------------------------------------------------
+static constexpr int kFilterDctN[] = {128, 256, 512, 1024, 2048, 4096, 8192};
+bool filter_dct_pow2_supported(int dtype, int n) {
+    for (int m : kFilterDctN) if (m == n) return filter_pow2_supported(dtype, n / 2);
+    return false;
+}
+template <int N> static int launch_filter_dct_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
+    if constexpr (N <= kFilterMaxN) {
+        if (dtype == NDFFT_F64) return vec_ok ? launch_filter_one<double, N, 2, FILTER_DCT>(f, s) : launch_filter_one<double, N, 1, FILTER_DCT>(f, s);
+        return vec_ok ? launch_filter_one<float, N, 4, FILTER_DCT>(f, s) : launch_filter_one<float, N, 1, FILTER_DCT>(f, s);
+    } else {
+        return fail(NDFFT_ERR_UNSUPPORTED, "dct filter kernel: unsupported n");
+    }
+}
+int launch_filter_dct_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s) {
+    const Pow2Args &a = f.a;
+    if (!filter_dct_pow2_supported(dtype, n)) return fail(NDFFT_ERR_UNSUPPORTED, "dct filter kernel: unsupported n");
+    const int64_t per16 = dtype == NDFFT_F64 ? 2 : 4;
+    const bool vec_ok = a.pitch_in % per16 == 0 && a.pitch_out % per16 == 0 && ((uintptr_t)a.in % 16) == 0 && ((uintptr_t)a.out % 16) == 0;
+    switch (n / 2) {
+#define NDFFT_CASE(N_, TPL_, ...) case N_: return launch_filter_dct_n<N_>(dtype, vec_ok, f, s);
+        NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
+#undef NDFFT_CASE
+        default: return fail(NDFFT_ERR_UNSUPPORTED, "dct filter kernel: unsupported n");
     }
 }
 

@@ -603,7 +603,7 @@ int get_filter_twiddles(const ndfft_plan *cplan, const void **out) {
     return NDFFT_OK;
 }
 
-int get_filter_r2c_tables(const ndfft_plan *cplan, const void **twp, const void **twp_rev, const void **wn) {
+int get_filter_r2c_tables(const ndfft_plan *cplan, const void **twp, const void **twp_rev, const void **wn, const void **c) {
     const DevTables *dt;
     int rc = get_dev_tables(cplan, &dt);
     if (rc) return rc;
@@ -620,6 +620,7 @@ int get_filter_r2c_tables(const ndfft_plan *cplan, const void **twp, const void 
     *twp = d.twp_filter_fwd;
     *twp_rev = d.twp_filter ? d.twp_filter : d.twp_filter_fwd;
     *wn = d.aux1;
+    if (c) *c = d.aux2;
     return NDFFT_OK;
 }
 

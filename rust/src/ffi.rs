@@ -89,6 +89,13 @@ extern "C" {
         shape: *const i64, stride_in: *const i64, stride_out: *const i64, axis: c_int,
         d_weights: *const c_void, n_weights: usize, norm: c_int, scale: f64, flags: c_int, stream: *mut c_void,
     ) -> c_int;
+    /// include/ndfft_mi355x_ext.h (ABI minor 6): out = s * DCT3(g (.) DCT2(in)) along `axis` in one call -- DCT plan, real arrays, n REAL weights; s = 1 (None), 4
+    /// (Default: each of the two calls pre-scales by 2) or `scale`.  Argument list, `flags` and in-place rule as for `ndfft_exec_filter_device`
+    pub fn ndfft_exec_dct_filter_device(
+        plan: *const ndfft_plan, d_input: *const c_void, d_output: *mut c_void, ndim: c_int,
+        shape: *const i64, stride_in: *const i64, stride_out: *const i64, axis: c_int,
+        d_weights: *const c_void, n_weights: usize, norm: c_int, scale: f64, flags: c_int, stream: *mut c_void,
+    ) -> c_int;
     pub fn ndfft_dev_alloc(d_ptr: *mut *mut c_void, bytes: usize) -> c_int;
     pub fn ndfft_dev_free(d_ptr: *mut c_void) -> c_int;
     pub fn ndfft_dev_upload(d_dst: *mut c_void, h_src: *const c_void, bytes: usize) -> c_int;

@@ -473,4 +473,23 @@ pub mod device {
                                                     weights: &DeviceArray<Complex<T>>, fuse: bool) {
         exec_filter_device(&handler.plan, input, output, axis, weights, filter_mode(&handler.norm), fuse);
     }
+    /// `output = DCT3(weights * DCT2(input))` along `axis`, lane by lane, in one call: what `nddct2`, a multiply of every lane by `weights` and `nddct3` give under the
+    /// handler's normalisation (None, or Default: each call pre-scales by 2, so 4 in all).  Unit-stride power-of-two lanes of 128..=8192 points at any offset and pitch
+    /// run one fused kernel, everything else `nddct2` + diagonal pass + `nddct3` (`fuse = false` forces that form).  `weights`: `n` real factors in device memory.
+    pub fn nddct_filter<T: FftNum + FloatConst>(input: &DeviceArray<T>, output: &mut DeviceArray<T>, handler: &DctHandler<T>, axis: usize, weights: &DeviceArray<T>, fuse: bool) {
+        check_axis(output.shape.len(), axis);
+        assert_eq!(input.shape, output.shape, "nddct_filter: input and output shapes differ");
+        let (si, sti) = input.geom();
+        let (_, sto) = output.geom();
+        let nw: usize = weights.shape.iter().product();
+        let mode = match &handler.norm {
+            Normalization::None => ffi::NDFFT_NORM_NONE,
+            Normalization::Default => ffi::NDFFT_NORM_DEFAULT,
+            _ => panic!("nddct_filter: the handler's normalisation must be None or Default"),
+        };
+        check(unsafe {
+            ffi::ndfft_exec_dct_filter_device(handler.plan.0, input.ptr, output.ptr, si.len() as c_int, si.as_ptr(), sti.as_ptr(), sto.as_ptr(), axis as c_int,
+                                              weights.ptr, nw, mode, 0.0, if fuse { 0 } else { ffi::NDFFT_FILTER_NO_FUSE }, std::ptr::null_mut())
+        });
+    }
 }

@@ -2,8 +2,8 @@
 """What ndfft_filter costs on the MI355X (needs the GPU; fails without one).
 
 Device-resident arrays, HBM-sourced over rotating (in, out) pairs whose inputs add up to at least 768 MiB (three times the Infinity Cache), timed with device
-events after a warm-up that also ramps the clock.  For c128 and c64 (an FftHandler) or f64 and f32 (real arrays under an R2cFftHandler, n // 2 + 1 weights) and
-the shapes 4096 x 4096, 16384 x 1024 and 65536 x 256 (lanes along axis 1), in the same run, in alternating blocks:
+events after a warm-up that also ramps the clock.  For c128 and c64 (an FftHandler), f64 and f32 (real arrays under an R2cFftHandler, n // 2 + 1 weights) or d64 and
+d32 (real arrays under a DctHandler: nddct_filter, n real weights; two_calls is nddct2 then nddct3) and the shapes 4096 x 4096, 16384 x 1024 and 65536 x 256 (lanes along axis 1), in the same run, in alternating blocks:
   two_calls   ndfft then ndifft (real: ndfft_r2c then ndifft_r2c) through a work array: code the filter does not touch, and a lower bound for any three-call
               form (the multiply is left out)
   composed    the filter with fuse=False: the forward transform into the spectrum image, the diagonal pass in place, the inverse
@@ -28,46 +28,52 @@ def main():
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--min-input-mib", type=int, default=768)
     ap.add_argument("--shapes", default="4096x4096,16384x1024,65536x256")
-    ap.add_argument("--dtypes", default="c128,c64", help="of c128, c64 (complex arrays) and f64, f32 (real arrays)")
+    ap.add_argument("--dtypes", default="c128,c64", help="of c128, c64 (complex arrays), f64, f32 (real arrays, R2C) and d64, d32 (real arrays, DCT)")
     args = ap.parse_args()
 
     import torch
     assert torch.cuda.is_available(), "bench_filter.py needs an MI355X"
-    from ndrustfft_amd import FftHandler, R2cFftHandler, _lib, ndfft, ndfft_filter, ndfft_r2c, ndifft, ndifft_r2c
+    from ndrustfft_amd import DctHandler, FftHandler, R2cFftHandler, _lib, nddct2, nddct3, nddct_filter, ndfft, ndfft_filter, ndfft_r2c, ndifft, ndifft_r2c
     L = _lib.default()
     rng = np.random.default_rng(7)
     results = []
     for dname in args.dtypes.split(","):
-        assert dname in ("c128", "c64", "f64", "f32"), dname
-        real = dname[0] == "f"
-        cdt, rdt, rnp = (torch.complex128, torch.float64, np.float64) if dname in ("c128", "f64") else (torch.complex64, torch.float32, np.float32)
+        assert dname in ("c128", "c64", "f64", "f32", "d64", "d32"), dname
+        dct = dname[0] == "d"
+        real = dname[0] == "f" or dct
+        cdt, rdt, rnp = (torch.complex128, torch.float64, np.float64) if dname in ("c128", "f64", "d64") else (torch.complex64, torch.float32, np.float32)
         adt = rdt if real else cdt
         for sh in args.shapes.split(","):
             rows, n = (int(v) for v in sh.split("x"))
             nbytes = rows * n * torch.empty((), dtype=adt).element_size()
             npairs = max(2, -(-(args.min_input_mib << 20) // nbytes))
-            h = R2cFftHandler(n, rnp) if real else FftHandler(n, rnp)
-            m = n // 2 + 1 if real else n                           # the spectrum lane
-            w = torch.from_numpy((rng.uniform(0.5, 2.0, m) * np.exp(2j * np.pi * rng.uniform(0, 1, m))).astype(np.complex128 if rnp is np.float64 else np.complex64)).to("cuda")
+            h = DctHandler(n, rnp) if dct else R2cFftHandler(n, rnp) if real else FftHandler(n, rnp)
+            m = n if dct else n // 2 + 1 if real else n             # the spectrum lane
+            if dct:
+                w = torch.from_numpy((rng.uniform(0.5, 2.0, m) * rng.choice([-1.0, 1.0], m)).astype(rnp)).to("cuda")
+            else:
+                w = torch.from_numpy((rng.uniform(0.5, 2.0, m) * np.exp(2j * np.pi * rng.uniform(0, 1, m))).astype(np.complex128 if rnp is np.float64 else np.complex64)).to("cuda")
             pairs = []
             for _ in range(npairs):
                 x = torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5
                 if not real:
                     x = torch.complex(x, torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5)
-                pairs.append((x, torch.zeros((rows, n), dtype=adt, device="cuda"), torch.zeros((rows, m), dtype=cdt, device="cuda")))
+                pairs.append((x, torch.zeros((rows, n), dtype=adt, device="cuda"), torch.zeros((rows, m), dtype=rdt if dct else cdt, device="cuda")))
             k = [0]
 
             def two_calls(x, y, work):
-                if real:
+                if dct:
+                    nddct2(x, work, h, 1); nddct3(work, y, h, 1)
+                elif real:
                     ndfft_r2c(x, work, h, 1); ndifft_r2c(work, y, h, 1)
                 else:
                     ndfft(x, work, h, 1); ndifft(work, y, h, 1)
 
             def composed(x, y, work):
-                ndfft_filter(x, y, h, 1, w, fuse=False)
+                (nddct_filter if dct else ndfft_filter)(x, y, h, 1, w, fuse=False)
 
             def fused(x, y, work):
-                ndfft_filter(x, y, h, 1, w)
+                (nddct_filter if dct else ndfft_filter)(x, y, h, 1, w)
             forms = {"two_calls": two_calls, "composed": composed, "fused": fused}
             routes = {}
 
