@@ -50,6 +50,8 @@ int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in,
  *
  * Checks: those of ndfft_exec_device for the plan's forward op, with the same panic texts in the same order; then a NULL d_weights, then n_weights (the message
  * names both numbers), then unknown bits in `flags` (all NDFFT_ERR_INVALID_ARG).  A refused call launches nothing and writes nothing.
+ * An array with a zero extent off the axis has no lane: as for ndfft_exec_device the call returns NDFFT_OK once the shapes agree, before it looks at the array
+ * pointers, the weights or the flags, and writes nothing (the same holds for ndfft_exec_dct_filter_device).
  * d_in == d_out with identical strides is the in-place filter and is safe on every route; any other overlap is undefined, as for ndfft_exec_device.
  * Asynchronous on `stream`; d_weights is read on `stream`.
  *
