@@ -856,7 +856,7 @@ int launch_jit_c2c(int dtype, const JitCfg &cfg_plan, int nt, const Pow2Args &a,
     const int c2c_thr = (int)NDFFT_DEV_INT("NDFFT_JIT_C2C_ROW_THREADS", 64);
     if (c2c_thr > 0 && cfg.row_lpb == 0) cfg.lpb = cfg.tpl >= c2c_thr ? 1 : std::max(1, c2c_thr / cfg.tpl);
     // f32 lanes exchange whole complex elements (64-bit LDS accesses, half the LDS instructions) as long as two
-    // workgroups still fit a CU, like the ahead-of-time f32 configurations (kernels_pow2.hip: Pow2Half).  Measured on
+    // workgroups still fit a CU, like the ahead-of-time f32 configurations (pow2_config.h: Pow2Half).  Measured on
     // 2^25 points (tools/probes/jit_f32_full.py): n = 1000 102 -> 96 us, 3000 141 -> 133, 6000 177 -> 137; but
     // n = 10000 (85 KiB: one workgroup per CU) 149 -> 172, hence the 80 KiB bound.
     const bool half = !(dtype == NDFFT_F32 && cfg.n >= jit_full_min() && (size_t)cfg.lpb * lane_pad_half(cfg.n) * 8 <= (size_t)80 * 1024);

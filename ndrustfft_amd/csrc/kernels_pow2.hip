@@ -23,59 +23,10 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "pow2_kernel.h"
+#include "pow2_config.h"
 #include "filter_kernel.h"
 
 namespace ndfft {
-
-// N, threads-per-lane, radices.  E = N / TPL must be a multiple of every radix.
-// f64 (16-byte elements, one element per global access)
-#define NDFFT_POW2_CONFIGS_F64(X) \
-    X(64, 8, 8, 8)            \
-    X(128, 8, 16, 8)          \
-    X(256, 16, 16, 16)        \
-    X(512, 64, 8, 8, 8)       \
-    X(1024, 64, 16, 8, 8)     \
-    X(2048, 128, 16, 16, 8)   \
-    X(4096, 512, 8, 8, 8, 8)  \
-    X(8192, 512, 8, 8, 8, 16) \
-    X(16384, 1024, 16, 16, 16, 4)
-// f32 (8-byte elements): first and last radix <= E/2 so that two adjacent elements (16 B) move per
-// global access (VEC = 2)
-#define NDFFT_POW2_CONFIGS_F32(X) \
-    X(64, 8, 8, 8)            \
-    X(128, 8, 8, 2, 8)        \
-    X(256, 16, 8, 4, 8)       \
-    X(512, 32, 8, 8, 8)       \
-    X(1024, 64, 8, 16, 8)     \
-    X(2048, 128, 8, 4, 8, 8)  \
-    X(4096, 256, 8, 8, 8, 8)  \
-    X(8192, 512, 8, 16, 8, 8) \
-    X(16384, 512, 16, 16, 8, 8)
-
-// threads per workgroup (whole lanes): a documented compile-time knob
-#ifndef NDFFT_POW2_ROW_THREADS
-#define NDFFT_POW2_ROW_THREADS 256
-#endif
-static constexpr int lpb_for(int tpl) { return tpl >= NDFFT_POW2_ROW_THREADS ? 1 : NDFFT_POW2_ROW_THREADS / tpl; }
-
-template <typename T, int N> struct Pow2Cfg;
-#define NDFFT_DEF_CFG64(N_, TPL_, ...) \
-    template <> struct Pow2Cfg<double, N_> { static constexpr int TPL = TPL_; using RL = RadixList<__VA_ARGS__>; };
-#define NDFFT_DEF_CFG32(N_, TPL_, ...) \
-    template <> struct Pow2Cfg<float, N_> { static constexpr int TPL = TPL_; using RL = RadixList<__VA_ARGS__>; };
-NDFFT_POW2_CONFIGS_F64(NDFFT_DEF_CFG64)
-NDFFT_POW2_CONFIGS_F32(NDFFT_DEF_CFG32)
-
-// LDS exchange: HALF (real parts, then imaginary parts, through one real-sized buffer) halves the footprint and
-// wins for f64 (occupancy).  f32 from n = 2048 up exchanges whole complex elements with 64-bit LDS accesses: half
-// the LDS instructions, and the footprint is that of the f64 half exchange anyway (measured after the packed-math
-// change, tools/kbench f32_halffull: 2048 83 -> 78 us, 4096 86 -> 80, 8192 93 -> 89, 16384 146 -> 126)
-template <typename T, int N> struct Pow2Half { static constexpr bool value = true; };
-template <> struct Pow2Half<float, 2048> { static constexpr bool value = false; };
-template <> struct Pow2Half<float, 4096> { static constexpr bool value = false; };
-template <> struct Pow2Half<float, 8192> { static constexpr bool value = false; };
-template <> struct Pow2Half<float, 16384> { static constexpr bool value = false; };
 
 bool pow2_supported(int dtype, int n) {
     (void)dtype;
@@ -122,18 +73,13 @@ bool stream_loads_for(size_t in_bytes) {
     return in_bytes > ((size_t)384 << 20);
 }
 
-// Position-split exchange (pow2_kernel.h: PSPLIT = 2) for the lengths whose lane fills a CU's LDS: two workgroups per CU instead of one.
-// NDFFT_PSPLIT=1 / 2 forces it off / on for n = 8192 and 16384 (A/B runs); default: the measured choice below.
-// Measured A-B-A-B on 2^24 points (profiles/r05/r05d_psplit_abab.txt): c64 n = 16384 65.5 -> 56.5 us (0.51 -> 0.59 of 8 TB/s), c64 n = 8192 51.8 -> 48.0 us
-// (0.65 -> 0.70); c128 n = 16384 unchanged (126 VGPRs x 1024 threads: registers, not LDS, keep it at one workgroup per CU), c128 n = 8192 -2 %.
-template <typename T, int N> struct Pow2PSplit { static constexpr int value = (sizeof(T) == 4 && N >= 8192) ? 2 : 1; };
+// Position-split exchange: pow2_config.h (Pow2PSplit); NDFFT_PSPLIT=1 / 2 forces it off / on for n = 8192 and 16384 (A/B runs)
 static int psplit_override() { return (int)NDFFT_DEV_INT("NDFFT_PSPLIT", 0); }
 
 template <typename T, int N, int NT, int VEC, int FL, int PS> static int launch_inst_ps(const Pow2Args &a0, hipStream_t s) {
     constexpr int TPL = Pow2Cfg<T, N>::TPL, LPB = lpb_for(TPL);
-    // FLAGS bit 4 from n = 4096: late passes whose twiddle table exceeds 32 KiB load W^k, W^2k, W^4k (, W^8k) and build
-    // the other powers (2-4 % on the instruction-bound long kernels; two extra roundings on those twiddles)
-    using K = Pow2Kernel<T, N, TPL, LPB, Pow2Half<T, N>::value, typename Pow2Cfg<T, N>::RL, FL | (N >= 4096 ? 16 : 0), 1, NT, VEC, PS>;
+    static_assert((FL & ~8) == 0, "callers choose the fused four-step form only; every other flag is pow2_config.h's choice");
+    using K = Pow2RowKernel<T, N, NT, VEC, (FL & 8) != 0, PS>;
     NDFFT_ENSURE_LDS_ATTR((k_pow2<K>));
     const int64_t nblk = (a0.nlanes + LPB - 1) / LPB;
     if (nblk <= 0) return NDFFT_OK;

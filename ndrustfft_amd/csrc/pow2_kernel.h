@@ -74,6 +74,9 @@ template <typename T, bool NT> __device__ __forceinline__ void gstore(cpx<T> *p,
 //   32 = LATENCY form (round 5): the twiddles of pass p + 1 are loaded BEFORE the exchange that follows pass p and the exchange's barriers wait for the LDS only
 //        (raw s_barrier behind s_waitcnt lgkmcnt(0); __syncthreads() would also drain the table loads), so the table's L2 round trip overlaps the exchange instead of
 //        following it.  Costs up to E - 1 complex registers across the exchange: for calls of few tiles, where one tile's latency is the call's (pow2_real.h: small grids)
+//   64 = (with 32) the latency form with DERIVED powers: a radix-8 / 16 pass loads W^k, W^2k, W^4k (, W^8k) only -- the rows bit 4 reads -- and builds the other powers after
+//        the exchange, so 3 (4) complex registers wait across it instead of R - 1; run() issues pass 1's loads right behind the data loads, pass p + 1's follow pass p's
+//        twiddle multiplies.  The loads are pinned there (tw_load) -- as plain loads the compiler sinks them back behind the exchange.  Row kernel only (run()).
 // NT: bit 0 = non-temporal stores, bit 1 = non-temporal loads
 // VEC = 2 (f32 only): global loads/stores move TWO adjacent complex elements (16 B) per lane; the
 //   first and last pass then own adjacent butterfly pairs j = 2t, 2t+1 instead of j = t, t+TPL.
@@ -83,6 +86,21 @@ template <typename T, bool NT> __device__ __forceinline__ void gstore(cpx<T> *p,
 //   barriers, half the LDS: n = 16384 then takes 70 KiB per lane instead of 139 KiB, i.e. TWO workgroups per CU, so that one lane's load /
 //   store phases overlap the other's exchanges (round 3; needs whole butterfly rounds and power-of-two sizes).
 // barrier of the exchange: LDS traffic only (see FLAGS bit 5)
+// Twiddle load of the derived latency form (FLAGS bit 6).  On the GPU each half is a relaxed wavefront-scope atomic load: the same global_load, no cache-policy bits
+// and no wait, but one the compiler neither sinks past the exchange's barriers nor merges; elsewhere (a build for another target, hiprtc) a plain load.
+template <typename T> __device__ __forceinline__ cpx<T> tw_load(const cpx<T> *p) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__HIPCC_RTC__) && !defined(NDFFT_LDS_BARRIER_OVERRIDE)
+    const double *d = (const double *)p;          // f64: real and imaginary part; f32: the whole element as one 8-byte load
+    if constexpr (sizeof(T) == 8) {
+        return mk<T>(__hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT), __hip_atomic_load(d + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
+    } else {
+        const double b = __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        cpx<T> r; __builtin_memcpy(&r, &b, sizeof(r)); return r;
+    }
+#else
+    return *p;
+#endif
+}
 template <bool RAW> __device__ __forceinline__ void xbar() {
 #ifdef NDFFT_LDS_BARRIER_OVERRIDE          // (a build for another target supplies its own LDS-only barrier)
     if constexpr (RAW) NDFFT_LDS_BARRIER_OVERRIDE();
@@ -93,6 +111,10 @@ template <bool RAW> __device__ __forceinline__ void xbar() {
 }
 template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS = 0, int MINW = 1, int NT = 1, int VEC = 1, int PSPLIT = 1> struct Pow2Kernel {
     static constexpr bool PREF = (FLAGS & 32) != 0;
+    static constexpr bool DERIVE = (FLAGS & 64) != 0;
+    static_assert(!DERIVE || PREF, "FLAGS bit 6 is a variant of the latency form (bit 5)");
+    // pass P waits for the power rows only (FLAGS bit 6; the other radices load whole tables)
+    static constexpr bool derived(int p) { return DERIVE && (RL::at(p) == 8 || RL::at(p) == 16); }
     static constexpr int MIN_WAVES = MINW;
     // Pass p has N / R_p butterflies, dealt to the TPL threads of the lane in SLOTS(p) rounds: j = t + q TPL.
     // When TPL does not divide N / R_p the last round is PARTIAL (threads with j >= N / R_p idle): that is what
@@ -121,8 +143,13 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
         for (int q = 0; q < NBF; ++q) {
             const int j = jof<P>(t, q), k = kmod<Ns>(j);
             if (full(P) || j < NB) {
+                if constexpr (derived(P)) {
 #pragma unroll
-                for (int r = 1; r < R; ++r) w[q * R + r] = tw[(r - 1) * Ns + k];
+                    for (int r = 1; r < R; r *= 2) w[q * R + r] = tw_load<T>(tw + (r - 1) * Ns + k);
+                } else {
+#pragma unroll
+                    for (int r = 1; r < R; ++r) w[q * R + r] = tw[(r - 1) * Ns + k];
+                }
             }
         }
     }
@@ -136,15 +163,24 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
         constexpr int R = RL::at(P), Ns = RL::ns(P), NBF = slots(P), NB = nbfly(P);
         constexpr bool FULL = full(P);
         constexpr bool TW_POWERS = (FLAGS & 16) != 0 && (size_t)(R - 1) * Ns * sizeof(cpx<T>) > 32 * 1024;
-        static_assert(!PREF || !TW_POWERS, "the latency form loads plain tables");
+        static_assert(!PREF || !TW_POWERS || DERIVE, "the latency form loads plain tables (bit 5 alone) or the power rows of every radix-8 / 16 pass (bits 5 + 6)");
         if constexpr (P > 0 && !(FLAGS & 1) && PREF) {
 #pragma unroll
             for (int q = 0; q < NBF; ++q) {
                 if (FULL || jof<P>(t, q) < NB) {
+                    if constexpr (derived(P)) {       // the arithmetic of TW_POWERS below
+                        cpx<T> *w = &wpre[q * R];
+                        w[3] = cmul(w[1], w[2]); w[5] = cmul(w[1], w[4]); w[6] = cmul(w[2], w[4]); w[7] = cmul(w[3], w[4]);
+                        if constexpr (R == 16) {
+#pragma unroll
+                            for (int r = 9; r < 16; ++r) w[r] = cmul(w[r - 8], w[8]);
+                        }
+                    }
 #pragma unroll
                     for (int r = 1; r < R; ++r) v[q * R + r] = cmul(v[q * R + r], wpre[q * R + r]);
                 }
             }
+            if constexpr (DERIVE && P + 1 < RL::NP) load_tw<P + 1>(wpre, twp, t);     // in flight during the butterflies and the exchange below
         } else
         if constexpr (P > 0 && !(FLAGS & 1)) {
             const cpx<T> *tw = twp + RL::twoff(P);
@@ -177,7 +213,7 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
         if constexpr (P + 1 < RL::NP) {
             constexpr int R2 = RL::at(P + 1), NB2 = N / R2, NBF2 = slots(P + 1);
             constexpr bool FULL2 = full(P + 1);
-            if constexpr (PREF && !(FLAGS & 1)) load_tw<P + 1>(wpre, twp, t);     // in flight during the exchange below
+            if constexpr (PREF && !DERIVE && !(FLAGS & 1)) load_tw<P + 1>(wpre, twp, t);     // in flight during the exchange below
             if constexpr (FLAGS & 2) {
             } else if constexpr (HALF) {
                 T *s = (T *)lds;
@@ -290,6 +326,9 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
                     }
             }
         }
+        // derived latency form: pass 1's power rows right behind the data loads -- vmcnt counts in order, so the wait for the data leaves them in flight
+        cpx<T> w[DERIVE ? E : 1];
+        if constexpr (DERIVE && RL::NP > 1 && !(FLAGS & 1)) load_tw<1>(w, (const cpx<T> *)a.twp, t);
         if (a.inverse) {
 #pragma unroll
             for (int i = 0; i < E; ++i) v[i].y = -v[i].y;
@@ -308,7 +347,8 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
                     }
                 }
         }
-        passes<0>(v, (const cpx<T> *)a.twp, lds, t);
+        if constexpr (DERIVE) passes_w<0>(v, (const cpx<T> *)a.twp, lds, t, w);
+        else passes<0>(v, (const cpx<T> *)a.twp, lds, t);
         if (!live) return;
         constexpr int RL_ = RL::at(RL::NP - 1), NBL = N / RL_, NBFL = slots(RL::NP - 1);
         if (a.inverse) {

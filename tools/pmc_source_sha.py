@@ -4,7 +4,7 @@ import hashlib
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["pow2_kernel.h", "butterflies.h", "device_common.h", "kernels_pow2.hip"]
+FILES = ["pow2_kernel.h", "pow2_config.h", "butterflies.h", "device_common.h", "kernels_pow2.hip"]
 
 
 def sha():
