@@ -194,6 +194,34 @@ def nddct3(input, output, handler, axis): _transform(_lib.OP_DCT3, input, output
 def nddct4(input, output, handler, axis): _transform(_lib.OP_DCT4, input, output, handler, axis)
 
 
+def _filter_device(name, symbol, abi_minor, handler, input, output, axis, weights, wlen, mode, fuse, resolve):
+    """The device half of ndfft_filter / nddct_filter: both arrays are torch tensors on the GPU and the argument types are checked.  `symbol`: the C entry point (ABI
+    minor `abi_minor`); `resolve`: the tensor method that clears the lazy bit the weights' dtype can carry (resolve_conj: complex, resolve_neg: real)."""
+    L = handler._L
+    if not hasattr(L.c, symbol):
+        raise _lib.NdfftError(_lib.ERR_UNSUPPORTED, f"this library build is older than ABI minor {abi_minor}: no {symbol}")
+    if input.device != output.device:
+        raise ValueError(f"input is on {input.device} but output is on {output.device}: both arrays must live on the same GPU")
+    if input is not output:
+        input = input.resolve_conj().resolve_neg()
+    if input.is_conj() or input.is_neg() or output.is_conj() or output.is_neg():
+        raise ValueError(f"a tensor written by the call has a lazy conj/neg bit set: pass a plain tensor (t.{resolve}())")
+    if list(input.shape) != list(output.shape) and axis < input.ndim:
+        raise _lib.Panic(_lib.ERR_SHAPE_MISMATCH, f"{name}: input shape {tuple(input.shape)} differs from output shape {tuple(output.shape)}")
+    with torch.cuda.device(output.device):
+        if _is_torch(weights):
+            if weights.device != output.device:
+                raise ValueError("weights must live on the arrays' GPU")
+            wd = getattr(weights, resolve)().contiguous()
+        else:
+            wd = torch.from_numpy(np.ascontiguousarray(weights)).to(output.device)     # (stream-ordered: the caching allocator keeps it alive for the stream's work)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(output.device).cuda_stream)
+        st = getattr(L.c, symbol)(handler._plan, ctypes.c_void_p(input.data_ptr()), ctypes.c_void_p(output.data_ptr()), input.ndim,
+                                  _i64(list(input.shape)), _i64(list(input.stride())), _i64(list(output.stride())), int(axis),
+                                  ctypes.c_void_p(wd.data_ptr()), wlen, mode, 0.0, 0 if fuse else _lib.FILTER_NO_FUSE, stream)
+    L.check(st)
+
+
 def ndfft_filter(input, output, handler, axis, weights, *, fuse=True):
     """output = IFFT(weights * FFT(input)) along `axis`, lane by lane: what ndfft -> `lane *= weights` -> ndifft give under the handler's normalisation (None:
     unscaled, Default: 1 / n), in one call.  handler: an FftHandler (complex arrays, n weights) or an R2cFftHandler (real arrays, n // 2 + 1 complex weights;
@@ -223,7 +251,6 @@ def ndfft_filter(input, output, handler, axis, weights, *, fuse=True):
         raise TypeError(f"weights: a vector of {cdt}")
     if int(weights.shape[0]) != wlen:
         raise ValueError(f"weights: got {int(weights.shape[0])} expected {wlen}")
-    L = handler._L
     mode = _lib.NORM_NONE if handler.norm.kind == Normalization.NONE else _lib.NORM_DEFAULT
     if not dev:
         if _is_torch(weights):
@@ -235,28 +262,7 @@ def ndfft_filter(input, output, handler, axis, weights, *, fuse=True):
         spec *= np.asarray(weights).reshape([wlen if d == axis else 1 for d in range(input.ndim)])
         inv(spec, output, handler, axis)
         return
-    if not hasattr(L.c, "ndfft_exec_filter_device"):
-        raise _lib.NdfftError(_lib.ERR_UNSUPPORTED, "this library build is older than ABI minor 5: no ndfft_exec_filter_device")
-    if input.device != output.device:
-        raise ValueError(f"input is on {input.device} but output is on {output.device}: both arrays must live on the same GPU")
-    if input is not output:
-        input = input.resolve_conj().resolve_neg()
-    if input.is_conj() or input.is_neg() or output.is_conj() or output.is_neg():
-        raise ValueError("a tensor written by the call has a lazy conj/neg bit set: pass a plain tensor (t.resolve_conj())")
-    if list(input.shape) != list(output.shape) and axis < input.ndim:
-        raise _lib.Panic(_lib.ERR_SHAPE_MISMATCH, f"ndfft_filter: input shape {tuple(input.shape)} differs from output shape {tuple(output.shape)}")
-    with torch.cuda.device(output.device):
-        if _is_torch(weights):
-            if weights.device != output.device:
-                raise ValueError("weights must live on the arrays' GPU")
-            wd = weights.resolve_conj().contiguous()
-        else:
-            wd = torch.from_numpy(np.ascontiguousarray(weights)).to(output.device)     # (stream-ordered: the caching allocator keeps it alive for the stream's work)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(output.device).cuda_stream)
-        st = L.c.ndfft_exec_filter_device(handler._plan, ctypes.c_void_p(input.data_ptr()), ctypes.c_void_p(output.data_ptr()), input.ndim,
-                                          _i64(list(input.shape)), _i64(list(input.stride())), _i64(list(output.stride())), int(axis),
-                                          ctypes.c_void_p(wd.data_ptr()), wlen, mode, 0.0, 0 if fuse else _lib.FILTER_NO_FUSE, stream)
-    L.check(st)
+    _filter_device("ndfft_filter", "ndfft_exec_filter_device", 5, handler, input, output, axis, weights, wlen, mode, fuse, "resolve_conj")
 
 
 def nddct_filter(input, output, handler, axis, weights, *, fuse=True):
@@ -286,7 +292,6 @@ def nddct_filter(input, output, handler, axis, weights, *, fuse=True):
         raise TypeError(f"weights: a vector of {rdt}")
     if int(weights.shape[0]) != n:
         raise ValueError(f"weights: got {int(weights.shape[0])} expected {n}")
-    L = handler._L
     mode = _lib.NORM_NONE if handler.norm.kind == Normalization.NONE else _lib.NORM_DEFAULT
     if not dev:
         if _is_torch(weights):
@@ -296,28 +301,7 @@ def nddct_filter(input, output, handler, axis, weights, *, fuse=True):
         coef *= np.asarray(weights).reshape([n if d == axis else 1 for d in range(input.ndim)])
         nddct3(coef, output, handler, axis)
         return
-    if not hasattr(L.c, "ndfft_exec_dct_filter_device"):
-        raise _lib.NdfftError(_lib.ERR_UNSUPPORTED, "this library build is older than ABI minor 6: no ndfft_exec_dct_filter_device")
-    if input.device != output.device:
-        raise ValueError(f"input is on {input.device} but output is on {output.device}: both arrays must live on the same GPU")
-    if input is not output:
-        input = input.resolve_conj().resolve_neg()
-    if input.is_conj() or input.is_neg() or output.is_conj() or output.is_neg():
-        raise ValueError("a tensor written by the call has a lazy conj/neg bit set: pass a plain tensor (t.resolve_neg())")
-    if list(input.shape) != list(output.shape) and axis < input.ndim:
-        raise _lib.Panic(_lib.ERR_SHAPE_MISMATCH, f"nddct_filter: input shape {tuple(input.shape)} differs from output shape {tuple(output.shape)}")
-    with torch.cuda.device(output.device):
-        if _is_torch(weights):
-            if weights.device != output.device:
-                raise ValueError("weights must live on the arrays' GPU")
-            wd = weights.resolve_neg().contiguous()
-        else:
-            wd = torch.from_numpy(np.ascontiguousarray(weights)).to(output.device)     # (stream-ordered: the caching allocator keeps it alive for the stream's work)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(output.device).cuda_stream)
-        st = L.c.ndfft_exec_dct_filter_device(handler._plan, ctypes.c_void_p(input.data_ptr()), ctypes.c_void_p(output.data_ptr()), input.ndim,
-                                              _i64(list(input.shape)), _i64(list(input.stride())), _i64(list(output.stride())), int(axis),
-                                              ctypes.c_void_p(wd.data_ptr()), n, mode, 0.0, 0 if fuse else _lib.FILTER_NO_FUSE, stream)
-    L.check(st)
+    _filter_device("nddct_filter", "ndfft_exec_dct_filter_device", 6, handler, input, output, axis, weights, n, mode, fuse, "resolve_neg")
 
 
 # #[cfg(feature = "parallel")] twins (lib.rs:374-421, 589-611, 777-844).  On one GPU every lane is processed in

@@ -212,7 +212,12 @@ void pow2_build_twiddles(int dtype, int n, HostTable &out);
 int launch_pow2(int dtype, int n, const Pow2Args &a, hipStream_t s);
 int xcd_chunk_for(size_t block_bytes, int64_t nblk);   // lane blocks per XCD chunk of the workgroup -> lane map (0: identity)
 bool stream_loads_for(size_t in_bytes);                // input larger than the Infinity Cache: streaming (nt) loads
-// ... and the fused filter on the same lanes (filter_kernel.h): FFT, times w, inverse FFT in one launch
+
+// kernels_filter.hip : the fused filter (filter_kernel.h) -- forward transform, times w, inverse transform in one launch, on the row kernel's lanes
+//   FILTER_C2C  complex lanes of n points under a C2C plan; FilterArgs::a as for launch_pow2
+//   FILTER_R2C  real lanes of n points under an R2C plan: the complex kernel of length n / 2; FilterArgs::a in COMPLEX elements
+//   FILTER_DCT  real lanes of n points under a DCT plan: out = s DCT3(g (.) DCT2(in)); FilterArgs::a in REAL elements, any base and pitch
+enum { FILTER_C2C = 0, FILTER_R2C = 1, FILTER_DCT = 2 };
 struct FilterArgs {
     Pow2Args a;              // in, out, nlanes, pitches, scale (of the inverse), twp (the plan's list), stream_in; `inverse` is not read
     const void *twp_rev;     // per-pass twiddles of the reversed list (= twp for a palindromic list)
@@ -220,16 +225,10 @@ struct FilterArgs {
     const void *wn = nullptr;   // real lanes only: W_n^k, k = 0 .. n / 2 (the R2C plan's aux1)
     const void *c = nullptr;    // DCT lanes only: e^{-i pi k/(2n)}, k < n (the DCT plan's aux2); w is then n REAL weights
 };
-bool filter_pow2_supported(int dtype, int n);
+bool filter_supported(int mode, int dtype, int n);                   // n: the handler length (n = 64 .. 4096 complex points, 128 .. 8192 reals)
+int launch_filter(int mode, int dtype, int n, const FilterArgs &f, hipStream_t s);
 void filter_pow2_build_twiddles(int dtype, int n, HostTable &out);   // twiddles of the reversed radix list (empty: the list is a palindrome, the plan's table serves)
-int launch_filter_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
-// ... and on real lanes of n points under an R2C plan (filter_kernel.h: REAL): the complex kernel of length n / 2; FilterArgs::a in COMPLEX elements
-bool filter_r2c_pow2_supported(int dtype, int n);
-void filter_r2c_build_twiddles(int dtype, int n, HostTable &fwd, HostTable &rev);   // per-pass twiddles of the length-n/2 list and of its reverse (empty: a palindrome)
-int launch_filter_r2c_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
-// ... and on real lanes of n points under a DCT plan (filter_kernel.h: FILTER_DCT): out = s DCT3(g (.) DCT2(in)); FilterArgs::a in REAL elements, any base and pitch
-bool filter_dct_pow2_supported(int dtype, int n);
-int launch_filter_dct_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s);
+void filter_r2c_build_twiddles(int dtype, int n, HostTable &fwd, HostTable &rev);   // real modes: per-pass twiddles of the length-n/2 list and of its reverse (empty: a palindrome)
 
 // kernels_wave.hip : LDS-free wavefront kernel (cross-lane shuffles) for dense C2C lanes of n = 2..64
 bool wave_supported(int n);

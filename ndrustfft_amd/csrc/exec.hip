@@ -2,7 +2,8 @@
 // Replaces the reference's lane iterator (create_transform! src/lib.rs:100-167 and its _par twin
 // 169-238): validation that mirrors the reference's panics, stride canonicalisation (the three
 // iterator strategies collapse into "every lane along `axis`, arbitrary signed strides") and kernel choice.  Host arrays are staged
-// through HBM by host.hip (ndfft_exec), which comes back here for prepare() and dispatch_peeled() (exec_internal.h).
+// through HBM by host.hip (ndfft_exec), which comes back here for prepare() and dispatch() (exec_internal.h); the calls composed of dispatch() and a pass
+// around it -- the batch-dim peel, Normalization::Weights, the filters -- are compose.hip's.
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -239,10 +240,11 @@ int current_ws(DeviceWs **out) {
 }
 static thread_local int g_input_hint = NDFFT_INPUT_AUTO;
 static thread_local int g_last_policy = -1;       // load policy the last call on this thread asked the model for (diagnostic)
+void reset_last_policy() { g_last_policy = -1; }
 static bool F_nt_ok(int F) { return F >= 64; }   // (short lanes: the staging loads are not 16-byte vectors on every path)
 // load policy for the dense C2C row kernels on input `in` (Pow2Args::stream_in), and the bookkeeping for the next call (the model: exec_internal.h, MallModel)
 static int row_load_policy(const void *in, size_t bytes, const void *out, size_t out_bytes);
-static int c2c_row_load_policy(const void *in, const void *out, size_t bytes) { return row_load_policy(in, bytes, out, bytes); }
+int c2c_row_load_policy(const void *in, const void *out, size_t bytes) { return row_load_policy(in, bytes, out, bytes); }
 static int row_load_policy(const void *in, size_t bytes, const void *out, size_t out_bytes) {
     const int force = sw().stream_loads;            // NDFFT_STREAM_LOADS: 0 / 1 forces a policy
     DeviceWs *ws;
@@ -256,7 +258,7 @@ static int row_load_policy(const void *in, size_t bytes, const void *out, size_t
     ws->mall.note_write(out, out_bytes);
     return nt ? 1 : 0;
 }
-static int get_scratch(int which, hipStream_t s, size_t bytes, void **out) {
+int get_scratch(int which, hipStream_t s, size_t bytes, void **out) {
     DeviceWs *ws;
     int rc = current_ws(&ws);
     if (rc) return rc;
@@ -269,8 +271,6 @@ static int get_scratch(int which, hipStream_t s, size_t bytes, void **out) {
     *out = sc.p;
     return NDFFT_OK;
 }
-
-static int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t stream);
 
 // (the result of a route: exec_internal.h, kDeclined)
 // A hiprtc launcher's NDFFT_ERR_UNSUPPORTED (no hiprtc, a failed compile or module load, NDFFT_JIT=cached with nothing cached) declines its route.
@@ -798,28 +798,6 @@ static int dispatch_transposed(const Problem &P, const void *d_in, void *d_out, 
     return transpose_batched(s2, d_out, outer, inner, n_out, p_out, inner, inner * p_out, n_out * inner, (int)eout, stream);
 }
 
-// The lane layout of one call: lane L = (o, i) with i the fastest batch dimension, element j of it at o * outer + i * lane + j * elem.
-// (dense compares the pitches with the lane lengths xlen / ylen: for C2C both are n)
-struct Layout {
-    bool rows;                       // unit element stride on both sides and one batch dimension at most: lanes at a uniform pitch
-    bool dense;                      // ... and that pitch is the lane length on both sides
-    bool cols;                       // the fastest batch dimension has unit stride on both sides: adjacent lanes are contiguous
-    int64_t pitch_in, pitch_out;     // stride of the slowest batch dimension (the lane pitch of rows), the lane length without one
-    int64_t inner;                   // extent of i (1 without a batch dimension)
-    int64_t lane_in, lane_out;       // stride of i (0 without a batch dimension)
-    int64_t outer_in, outer_out;     // stride of o: the slower of two batch dimensions (0 with fewer)
-    explicit Layout(const Problem &P) {
-        const size_t nb = P.b.size();
-        rows = P.xs == 1 && P.ys == 1 && nb <= 1;
-        pitch_in = nb ? P.b[0].sin : P.xlen; pitch_out = nb ? P.b[0].sout : P.ylen;
-        dense = rows && pitch_in == P.xlen && pitch_out == P.ylen;
-        cols = nb && P.b.back().sin == 1 && P.b.back().sout == 1;
-        inner = nb ? P.b.back().shape : 1;
-        lane_in = nb ? P.b.back().sin : 0; lane_out = nb ? P.b.back().sout : 0;
-        outer_in = nb == 2 ? P.b[0].sin : 0; outer_out = nb == 2 ? P.b[0].sout : 0;
-    }
-};
-
 // one dispatch(): what every route reads
 struct Call {
     const Problem &P;
@@ -913,7 +891,7 @@ static Pow2Args c2c_row_args(const Call &k) {
     return a;
 }
 
-// tuned path: contiguous power-of-two C2C lanes at a uniform pitch (the predicate is also the fused filter's: filter_fused)
+// tuned path: contiguous power-of-two C2C lanes at a uniform pitch (the fused filters take the same lanes: compose.hip, filter_fused)
 static bool pow2_rows_eligible(const Call &k) { return k.plan->kind == NDFFT_KIND_C2C && k.plan->cfg[CFG_MAIN].pow2 && k.L.rows; }
 static int route_pow2_rows(const Call &k) {
     if (!pow2_rows_eligible(k)) return kDeclined;
@@ -1074,7 +1052,7 @@ static int route_long(const Call &k) {
 }
 
 // a route that ran another dispatch() inside: its path is "<prefix><inner path>"
-static int prefixed(const char *prefix, int rc) {
+int prefixed(const char *prefix, int rc) {
     if (rc == NDFFT_OK) {
         static thread_local std::string path;
         path = std::string(prefix) + last_path();
@@ -1123,7 +1101,7 @@ static int route_packed(const Call &k) {
 }
 
 // the routes in order of preference; the generic LDS kernel takes whatever none of them does
-static int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t stream) {
+int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t stream) {
     const DevTables *dt;
     int rc = get_dev_tables(P.plan, &dt);
     if (rc) return rc;
@@ -1132,220 +1110,6 @@ static int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t
                                        route_real_engine, route_long, route_transposed, route_packed})
         if ((rc = route(k)) != kDeclined) return rc;
     return k.f32() ? dispatch_generic<float>(P, d_in, d_out, *dt, stream) : dispatch_generic<double>(P, d_in, d_out, *dt, stream);
-}
-
-// more than kMaxBatchDims un-mergeable batch dims: peel the slowest ones on the host
-int dispatch_peeled(Problem &P, const char *d_in, char *d_out, size_t ein, size_t eout, hipStream_t stream) {
-    if (P.b.size() <= (size_t)kMaxBatchDims) return dispatch(P, d_in, d_out, stream);
-    BatchDim outer = P.b.front();
-    Problem Q = P;
-    Q.b.erase(Q.b.begin());
-    Q.nlanes = P.nlanes / outer.shape;
-    for (int64_t i = 0; i < outer.shape; ++i) {
-        int rc = dispatch_peeled(Q, d_in + i * outer.sin * (int64_t)ein, d_out + i * outer.sout * (int64_t)eout, ein, eout, stream);
-        if (rc) return rc;
-    }
-    return NDFFT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Normalization::Weights (ndfft_exec_weighted_device): the diagonal pass of weights_kernel.h around dispatch(), at the reference's
-// application points.  The transform itself runs with scale 1 on the route it would take anyway.
-// ---------------------------------------------------------------------------------------------
-static void lane_geoms(const Problem &P, LaneGeom &gi, LaneGeom &go) {
-    gi.axis_stride = P.xs; go.axis_stride = P.ys; gi.nb = go.nb = (int32_t)P.b.size(); gi.pad_ = go.pad_ = 0;
-    for (size_t i = 0; i < P.b.size(); ++i) { gi.bshape[i] = go.bshape[i] = P.b[i].shape; gi.bstride[i] = P.b[i].sin; go.bstride[i] = P.b[i].sout; }
-}
-// a route followed by the weight pass: its path is "<route>+weights"
-static int suffixed(int rc, const char *suffix) {
-    if (rc == NDFFT_OK) {
-        static thread_local std::string path;
-        path = std::string(last_path()) + suffix;
-        set_last_path(path.c_str());
-    }
-    return rc;
-}
-// one problem of <= kMaxBatchDims batch dims
-static int weighted(const Problem &P, const char *d_in, char *d_out, const void *d_w, hipStream_t stream) {
-    const int dtype = P.plan->dtype;
-    int rc;
-    LaneGeom gi, go;
-    if (P.op == NDFFT_OP_C2C_INV) {
-        // after, on the output lane (lib.rs:326-330): in place on the output view, the final result -> streaming stores like the transform kernels' own
-        if ((rc = dispatch(P, d_in, d_out, stream))) return rc;
-        lane_geoms(P, gi, go);
-        return suffixed(launch_weights(d_out, d_out, d_w, go, go, P.ylen, dtype, 1, 1, stream), "+weights");
-    }
-    // before, on the input lane (lib.rs:511-515, 692-696): caller's input -> a dense image IN THE INPUT'S OWN DIMENSION ORDER (dims sorted by |stride| get dense
-    // positive strides; a broadcast BATCH dim keeps stride 0 and is not materialised), so that the transform takes the route it would take on the caller's array
-    const int cplx = op_in_cplx(P.op) ? 1 : 0;
-    const size_t ein = real_size(dtype) * (cplx ? 2 : 1);
-    Problem Q = P;
-    const int nd = (int)P.b.size() + 1;            // index nd - 1: the axis
-    int order[kMaxBatchDims + 1];
-    auto stride_of = [&](int i) { return i == nd - 1 ? P.xs : P.b[i].sin; };
-    auto shape_of = [&](int i) { return i == nd - 1 ? P.xlen : P.b[i].shape; };
-    for (int i = 0; i < nd; ++i) order[i] = i;
-    std::stable_sort(order, order + nd, [&](int a, int b) {
-        const int64_t sa = std::llabs(stride_of(a)), sb = std::llabs(stride_of(b));
-        return sa != sb ? sa < sb : a > b;           // equal strides (extent-1 lanes): the later dim is the faster one, as in C order
-    });
-    int64_t run = 1;
-    for (int k = 0; k < nd; ++k) {
-        const int i = order[k];
-        // (only a BATCH dim may stay broadcast: a diagonal does not commute with broadcasting along the lane, x * w[j] differs from j to j, so the axis is always materialised)
-        const int64_t st = i != nd - 1 && stride_of(i) == 0 ? 0 : run;
-        if (st) run *= shape_of(i);
-        if (i == nd - 1) Q.xs = st; else Q.b[i].sin = st;
-    }
-    void *S;
-    if ((rc = get_scratch(8, stream, (size_t)run * ein, &S))) return rc;
-    DeviceWs *ws;
-    if ((rc = current_ws(&ws))) return rc;
-    lane_geoms(P, gi, go);
-    LaneGeom gq, unused;
-    lane_geoms(Q, gq, unused);
-    // the image is read again at once by the transform: plain, cache-allocating stores
-    if ((rc = launch_weights(d_in, S, d_w, gi, gq, P.xlen, dtype, cplx, 0, stream))) return rc;
-    // Speed only: what the row kernels' load policy should expect of the image.  Noted BEFORE dispatch() on purpose, so that a route with a load policy sees the image as
-    // just written (small: resident, plain loads; above 64 MiB: streaming loads); that route's own row_load_policy then notes the read.  Routes without a policy leave the
-    // read un-noted.  Neither choice has been measured against the alternative.
-    ws->mall.note_write(S, (size_t)run * ein);
-    return prefixed("weights+", dispatch(Q, S, d_out, stream));
-}
-// more than kMaxBatchDims un-mergeable batch dims: peeled on the host like dispatch_peeled; every piece is weighted
-static int weighted_peeled(Problem &P, const char *d_in, char *d_out, size_t ein, size_t eout, const void *d_w, hipStream_t stream) {
-    if (P.b.size() <= (size_t)kMaxBatchDims) return weighted(P, d_in, d_out, d_w, stream);
-    BatchDim outer = P.b.front();
-    Problem Q = P;
-    Q.b.erase(Q.b.begin());
-    Q.nlanes = P.nlanes / outer.shape;
-    for (int64_t i = 0; i < outer.shape; ++i) {
-        int rc = weighted_peeled(Q, d_in + i * outer.sin * (int64_t)ein, d_out + i * outer.sout * (int64_t)eout, ein, eout, d_w, stream);
-        if (rc) return rc;
-    }
-    return NDFFT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// ndfft_filter (ndfft_exec_filter_device): out = s IFFT(w (.) FFT(in)) along the axis.  P is the FORWARD problem from the caller's input geometry to the caller's
-// OUTPUT geometry (sin / xs: input strides, sout / ys: output strides; for an R2C plan P.ylen is the half spectrum's length, the output lane has P.xlen reals).
-// ---------------------------------------------------------------------------------------------
-// fused: lanes on which dispatch() would run pow2_reg in both directions, n <= 4096 -- one launch, no scratch, no allocation after the first call of a plan whose
-// radix list is no palindrome (get_filter_twiddles).  R2C plans: real lanes of n = 128 .. 8192 at unit stride and a uniform pitch, read as n / 2 complex points
-// (path filter_r2c_pow2) -- every lane base must then be a whole complex element: bases multiples of 2 sizeof(T), even pitches.  The first call of a plan builds
-// and uploads the tables of the length-n/2 list (get_filter_r2c_tables); later calls allocate nothing.  DCT plans (ndfft_exec_dct_filter_device): the same lanes and the
-// same tables plus the plan's aux2, path filter_dct_pow2, with NO alignment condition -- the kernel reads and writes the lane as reals
-static int filter_fused(const Problem &P, const char *d_in, char *d_out, const void *d_w, hipStream_t stream) {
-    const DevTables *dt;
-    int rc = get_dev_tables(P.plan, &dt);
-    if (rc) return rc;
-    const Call k(P, d_in, d_out, stream, *dt);
-    if (k.plan->kind == NDFFT_KIND_DCT) {
-        if (!(k.L.rows && filter_dct_pow2_supported(k.plan->dtype, k.n))) return kDeclined;
-        FilterArgs f;
-        f.a.in = d_in; f.a.out = d_out; f.a.nlanes = P.nlanes; f.a.pitch_in = k.L.pitch_in; f.a.pitch_out = k.L.pitch_out;   // in reals
-        f.a.inverse = 0; f.a.scale = P.scale;
-        f.w = d_w;
-        if ((rc = get_filter_r2c_tables(P.plan, &f.a.twp, &f.twp_rev, &f.wn, &f.c))) return rc;
-        if (k.L.dense) f.a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)P.nlanes * k.plan->n * real_size(k.plan->dtype));
-        set_last_path("filter_dct_pow2");
-        return launch_filter_dct_pow2(k.plan->dtype, k.n, f, stream);
-    }
-    if (k.plan->kind == NDFFT_KIND_R2C) {
-        const size_t r = real_size(k.plan->dtype);
-        const int64_t pin = P.b.empty() ? k.n : P.b[0].sin, pout = P.b.empty() ? k.n : P.b[0].sout;   // in reals (Layout's pitch_out is the half spectrum's without a batch dim)
-        if (!(k.L.rows && filter_r2c_pow2_supported(k.plan->dtype, k.n) && pin % 2 == 0 && pout % 2 == 0 && (uintptr_t)d_in % (2 * r) == 0 && (uintptr_t)d_out % (2 * r) == 0))
-            return kDeclined;
-        FilterArgs f;
-        f.a.in = d_in; f.a.out = d_out; f.a.nlanes = P.nlanes; f.a.pitch_in = pin / 2; f.a.pitch_out = pout / 2;
-        f.a.inverse = 0; f.a.scale = P.scale;
-        f.w = d_w;
-        if ((rc = get_filter_r2c_tables(P.plan, &f.a.twp, &f.twp_rev, &f.wn))) return rc;
-        if (pin == k.n && pout == k.n) f.a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)P.nlanes * k.plan->n * r);
-        set_last_path("filter_r2c_pow2");
-        return launch_filter_r2c_pow2(k.plan->dtype, k.n, f, stream);
-    }
-    if (!(pow2_rows_eligible(k) && filter_pow2_supported(k.plan->dtype, k.n))) return kDeclined;
-    FilterArgs f;
-    f.a = c2c_row_args(k);
-    f.w = d_w;
-    if ((rc = get_filter_twiddles(P.plan, &f.twp_rev))) return rc;
-    if (k.L.dense) f.a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)P.nlanes * k.plan->n * 2 * real_size(k.plan->dtype));
-    set_last_path("filter_pow2");
-    return launch_filter_pow2(k.plan->dtype, k.n, f, stream);
-}
-// adjacent batch dims that are contiguous in both views become one (as prepare() does)
-static void remerge(Problem &Q) {
-    std::vector<BatchDim> b;
-    for (const BatchDim &d : Q.b) {
-        if (!b.empty() && b.back().sin == d.shape * d.sin && b.back().sout == d.shape * d.sout) { b.back().shape *= d.shape; b.back().sin = d.sin; b.back().sout = d.sout; continue; }
-        b.push_back(d);
-    }
-    Q.b.swap(b);
-}
-// composed, one problem of <= kMaxBatchDims batch dims: forward dispatch() into a dense spectrum image S (in the input's own dimension order, as weighted() builds its
-// image, but with every dim materialised: the spectrum of a broadcast lane is written once per index), the diagonal pass in place on S (cache-allocating stores: the
-// inverse reads it at once), inverse dispatch() from S into the caller's output.  S is scratch slot 8, which no route's own scratch aliases.  Safe in place: the whole
-// input is in S before the inverse writes.  The two ops and the element of S come from the plan kind: C2C forward / inverse and R2C / C2R through a complex image with
-// complex weights, DCT-II / DCT-III through a REAL image with real weights (the diagonal pass in the form Normalization::Weights uses for the DCT ops).
-static int filter_composed(const Problem &P, const char *d_in, char *d_out, const void *d_w, double scale, hipStream_t stream) {
-    const int dtype = P.plan->dtype;
-    const bool r2c = P.plan->kind == NDFFT_KIND_R2C, dct = P.plan->kind == NDFFT_KIND_DCT;
-    const size_t ec = (dct ? 1 : 2) * real_size(dtype);
-    const int nd = (int)P.b.size() + 1;            // index nd - 1: the axis
-    int order[kMaxBatchDims + 1];
-    auto stride_of = [&](int i) { return i == nd - 1 ? P.xs : P.b[i].sin; };
-    for (int i = 0; i < nd; ++i) order[i] = i;
-    std::stable_sort(order, order + nd, [&](int a, int b) {
-        const int64_t sa = std::llabs(stride_of(a)), sb = std::llabs(stride_of(b));
-        return sa != sb ? sa < sb : a > b;
-    });
-    Problem F = P, I = P;                          // F: caller's input -> S;  I: S -> caller's output
-    F.op = dct ? NDFFT_OP_DCT2 : r2c ? NDFFT_OP_R2C : NDFFT_OP_C2C_FWD; F.scale = 1.0;
-    I.op = dct ? NDFFT_OP_DCT3 : r2c ? NDFFT_OP_C2R : NDFFT_OP_C2C_INV; I.scale = scale; I.xlen = P.ylen; I.ylen = P.xlen;
-    int64_t run = 1;
-    for (int k = 0; k < nd; ++k) {
-        const int i = order[k];
-        if (i == nd - 1) { F.ys = I.xs = run; run *= P.ylen; }
-        else { F.b[i].sout = I.b[i].sin = run; run *= P.b[i].shape; }
-    }
-    remerge(F); remerge(I);
-    void *S;
-    int rc;
-    if ((rc = get_scratch(8, stream, (size_t)run * ec, &S))) return rc;
-    DeviceWs *ws;
-    if ((rc = current_ws(&ws))) return rc;
-    if ((rc = dispatch(F, d_in, S, stream))) return rc;
-    static thread_local std::string path;
-    const std::string fwd = last_path();
-    LaneGeom gs, unused;
-    lane_geoms(I, gs, unused);
-    if ((rc = launch_weights(S, S, d_w, gs, gs, P.ylen, dtype, dct ? 0 : 1, 0, stream))) return rc;
-    ws->mall.note_write(S, (size_t)run * ec);      // (speed only, as in weighted(): what a row kernel's load policy should expect of the image)
-    if ((rc = dispatch(I, S, d_out, stream))) return rc;
-    path = fwd + "+weights+" + last_path();
-    set_last_path(path.c_str());
-    return NDFFT_OK;
-}
-// more than kMaxBatchDims un-mergeable batch dims: peeled on the host like weighted_peeled
-static int filter_peeled(Problem &P, const char *d_in, char *d_out, size_t esz, const void *d_w, double scale, bool fuse, hipStream_t stream) {
-    if (P.b.size() <= (size_t)kMaxBatchDims) {
-        if (fuse) {
-            const int rc = filter_fused(P, d_in, d_out, d_w, stream);
-            if (rc != kDeclined) return rc;
-        }
-        return filter_composed(P, d_in, d_out, d_w, scale, stream);
-    }
-    BatchDim outer = P.b.front();
-    Problem Q = P;
-    Q.b.erase(Q.b.begin());
-    Q.nlanes = P.nlanes / outer.shape;
-    for (int64_t i = 0; i < outer.shape; ++i) {
-        int rc = filter_peeled(Q, d_in + i * outer.sin * (int64_t)esz, d_out + i * outer.sout * (int64_t)esz, esz, d_w, scale, fuse, stream);
-        if (rc) return rc;
-    }
-    return NDFFT_OK;
 }
 
 }  // namespace ndfft
@@ -1358,7 +1122,7 @@ int ndfft_exec_device(const ndfft_plan *plan, int op, const void *d_in, void *d_
                       const int64_t *shape_in, const int64_t *stride_in, const int64_t *shape_out,
                       const int64_t *stride_out, int axis, int norm, double scale, void *stream) {
     clear_err();
-    g_last_policy = -1;
+    reset_last_policy();
     Problem P;
     bool nothing;
     int rc = prepare(plan, op, ndim, shape_in, stride_in, shape_out, stride_out, axis, norm, scale, P, nothing);
@@ -1367,86 +1131,6 @@ int ndfft_exec_device(const ndfft_plan *plan, int op, const void *d_in, void *d_
     const size_t r = real_size(plan->dtype);
     return dispatch_peeled(P, (const char *)d_in, (char *)d_out, op_in_cplx(op) ? 2 * r : r, op_out_cplx(op) ? 2 * r : r,
                            (hipStream_t)stream);
-}
-
-int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in, void *d_out, int ndim,
-                               const int64_t *shape_in, const int64_t *stride_in, const int64_t *shape_out,
-                               const int64_t *stride_out, int axis, const void *d_weights, size_t n_weights, void *stream) {
-    clear_err();
-    g_last_policy = -1;
-    Problem P;
-    bool nothing;
-    int rc = prepare(plan, op, ndim, shape_in, stride_in, shape_out, stride_out, axis, NDFFT_NORM_NONE, 0.0, P, nothing);
-    if (rc || nothing) return rc;
-    if (!d_in || !d_out) return fail(NDFFT_ERR_INVALID_ARG, "null array pointer");
-    const size_t r = real_size(plan->dtype);
-    const size_t ein = op_in_cplx(op) ? 2 * r : r, eout = op_out_cplx(op) ? 2 * r : r;
-    if (op == NDFFT_OP_C2C_FWD || op == NDFFT_OP_R2C)   // the forward lane methods never look at the normalisation (lib.rs:313-318, 497-503)
-        return dispatch_peeled(P, (const char *)d_in, (char *)d_out, ein, eout, (hipStream_t)stream);
-    if (!d_weights) return fail(NDFFT_ERR_INVALID_ARG, "null weights pointer");
-    const int64_t want = op == NDFFT_OP_C2C_INV ? P.ylen : P.xlen;
-    if ((int64_t)n_weights != want) {
-        char m[128];
-        snprintf(m, sizeof m, "weights: got %zu expected %lld (the length of the weighted lane)", n_weights, (long long)want);
-        return fail(NDFFT_ERR_INVALID_ARG, m);
-    }
-    return weighted_peeled(P, (const char *)d_in, (char *)d_out, ein, eout, d_weights, (hipStream_t)stream);
-}
-
-int ndfft_exec_filter_device(const ndfft_plan *plan, const void *d_in, void *d_out, int ndim, const int64_t *shape, const int64_t *stride_in,
-                             const int64_t *stride_out, int axis, const void *d_weights, size_t n_weights, int norm, double scale, int flags, void *stream) {
-    clear_err();
-    g_last_policy = -1;
-    // the checks of ndfft_exec_device for the plan's forward op (a DCT plan has none here: "op does not belong to this plan's handler kind"); the forward op of an
-    // R2C plan maps the caller's real lane to a half spectrum, so its output extent along the axis is n / 2 + 1 whatever the caller's is
-    const bool r2c = plan && plan->kind == NDFFT_KIND_R2C;
-    int64_t shape_mid[NDFFT_MAX_DIMS];
-    const int64_t *shape_out = shape;
-    if (r2c && shape && ndim > 0 && ndim <= NDFFT_MAX_DIMS && axis >= 0 && axis < ndim) {
-        for (int d = 0; d < ndim; ++d) shape_mid[d] = shape[d];
-        shape_mid[axis] = (int64_t)plan->n / 2 + 1;
-        shape_out = shape_mid;
-    }
-    Problem P;
-    bool nothing;
-    int rc = prepare(plan, r2c ? NDFFT_OP_R2C : NDFFT_OP_C2C_FWD, ndim, shape, stride_in, shape_out, stride_out, axis, norm, scale, P, nothing);
-    if (rc || nothing) return rc;
-    if (!d_in || !d_out) return fail(NDFFT_ERR_INVALID_ARG, "null array pointer");
-    if (!d_weights) return fail(NDFFT_ERR_INVALID_ARG, "null weights pointer");
-    if ((int64_t)n_weights != P.ylen) {
-        char m[128];
-        snprintf(m, sizeof m, "weights: got %zu expected %lld (the length of the spectrum lane)", n_weights, (long long)P.ylen);
-        return fail(NDFFT_ERR_INVALID_ARG, m);
-    }
-    if (flags & ~NDFFT_FILTER_NO_FUSE) return fail(NDFFT_ERR_INVALID_ARG, "unknown filter flag");
-    const double s = norm == NDFFT_NORM_NONE ? 1.0 : norm == NDFFT_NORM_DEFAULT ? 1.0 / (double)plan->n : scale;
-    P.scale = s;                                   // (the fused kernel's; the composed route sets its two problems' own)
-    const size_t r = real_size(plan->dtype);
-    return filter_peeled(P, (const char *)d_in, (char *)d_out, r2c ? r : 2 * r, d_weights, s, !(flags & NDFFT_FILTER_NO_FUSE), (hipStream_t)stream);
-}
-
-int ndfft_exec_dct_filter_device(const ndfft_plan *plan, const void *d_in, void *d_out, int ndim, const int64_t *shape, const int64_t *stride_in,
-                                 const int64_t *stride_out, int axis, const void *d_weights, size_t n_weights, int norm, double scale, int flags, void *stream) {
-    clear_err();
-    g_last_policy = -1;
-    // the checks of ndfft_exec_device for NDFFT_OP_DCT2 (a C2C or an R2C plan has no such op: "op does not belong to this plan's handler kind")
-    Problem P;
-    bool nothing;
-    int rc = prepare(plan, NDFFT_OP_DCT2, ndim, shape, stride_in, shape, stride_out, axis, norm, scale, P, nothing);
-    if (rc || nothing) return rc;
-    if (!d_in || !d_out) return fail(NDFFT_ERR_INVALID_ARG, "null array pointer");
-    if (!d_weights) return fail(NDFFT_ERR_INVALID_ARG, "null weights pointer");
-    if ((int64_t)n_weights != P.ylen) {
-        char m[128];
-        snprintf(m, sizeof m, "weights: got %zu expected %lld (the length of the coefficient lane)", n_weights, (long long)P.ylen);
-        return fail(NDFFT_ERR_INVALID_ARG, m);
-    }
-    if (flags & ~NDFFT_FILTER_NO_FUSE) return fail(NDFFT_ERR_INVALID_ARG, "unknown filter flag");
-    // nddct2 and nddct3 each pre-scale their input by 2 under Default (lib.rs:700-722, 736-741): both factors are exact, so the pair's is 4
-    const double s = norm == NDFFT_NORM_NONE ? 1.0 : norm == NDFFT_NORM_DEFAULT ? 4.0 : scale;
-    P.scale = s;                                   // (the fused kernel's; the composed route sets its two problems' own)
-    const size_t r = real_size(plan->dtype);
-    return filter_peeled(P, (const char *)d_in, (char *)d_out, r, d_weights, s, !(flags & NDFFT_FILTER_NO_FUSE), (hipStream_t)stream);
 }
 
 int ndfft_last_input_policy(void) { return g_last_policy; }
@@ -1471,4 +1155,8 @@ int ndfft_release_workspace(void) {
 // existed does not name it and would link a library without ndfft_exec: such a build gets the host-array call through this unit.
 #ifndef NDFFT_HOST_UNIT
 #include "host.hip"
+#endif
+// ... and so is compose.hip (-DNDFFT_COMPOSE_UNIT): an older list gets dispatch_peeled and the weighted and filter calls through this unit
+#ifndef NDFFT_COMPOSE_UNIT
+#include "compose.hip"
 #endif

@@ -1,5 +1,5 @@
-// exec_internal.h -- what exec.hip (device dispatch) shares with host.hip (the host-array call): one canonicalised problem, its
-// dispatch, and the per-thread, per-device workspace.  Included by those two units only.
+// exec_internal.h -- what exec.hip (device dispatch) shares with compose.hip (the weighted and filter calls, the batch-dim peel) and host.hip (the
+// host-array call): one canonicalised problem, its dispatch, and the per-thread, per-device workspace.  Included by those three units only.
 #pragma once
 #include "engine.h"
 
@@ -28,8 +28,41 @@ inline bool op_out_cplx(int op) { return op == NDFFT_OP_C2C_FWD || op == NDFFT_O
 // validation shared by the host and device entry points; fills Problem.  `nothing`: the call is valid and has nothing to do.
 int prepare(const ndfft_plan *plan, int op, int ndim, const int64_t *shape_in, const int64_t *stride_in, const int64_t *shape_out,
             const int64_t *stride_out, int axis, int norm, double scale, Problem &P, bool &nothing);
-// runs one problem on device arrays; more than kMaxBatchDims un-mergeable batch dims are peeled on the host
+// runs one problem on device arrays; more than kMaxBatchDims un-mergeable batch dims are peeled on the host (compose.hip)
 int dispatch_peeled(Problem &P, const char *d_in, char *d_out, size_t ein, size_t eout, hipStream_t stream);
+
+// ---- exec.hip, for compose.hip ----
+// one problem of at most kMaxBatchDims batch dims on the first route that takes it
+int dispatch(const Problem &P, const void *d_in, void *d_out, hipStream_t stream);
+// a route that ran another dispatch() inside: its path is "<prefix><inner path>"
+int prefixed(const char *prefix, int rc);
+// scratch array `which` (DeviceWs::scratch) of this thread on stream s, at least `bytes` long
+int get_scratch(int which, hipStream_t s, size_t bytes, void **out);
+// load policy of a dense row kernel that reads `bytes` at `in` and writes as many at `out` (Pow2Args::stream_in), and the model's bookkeeping for the next call
+int c2c_row_load_policy(const void *in, const void *out, size_t bytes);
+void reset_last_policy();         // every entry point, first thing: ndfft_last_input_policy answers for this call
+
+// The lane layout of one call: lane L = (o, i) with i the fastest batch dimension, element j of it at o * outer + i * lane + j * elem.
+// (dense compares the pitches with the lane lengths xlen / ylen: for C2C both are n)
+struct Layout {
+    bool rows;                       // unit element stride on both sides and one batch dimension at most: lanes at a uniform pitch
+    bool dense;                      // ... and that pitch is the lane length on both sides
+    bool cols;                       // the fastest batch dimension has unit stride on both sides: adjacent lanes are contiguous
+    int64_t pitch_in, pitch_out;     // stride of the slowest batch dimension (the lane pitch of rows), the lane length without one
+    int64_t inner;                   // extent of i (1 without a batch dimension)
+    int64_t lane_in, lane_out;       // stride of i (0 without a batch dimension)
+    int64_t outer_in, outer_out;     // stride of o: the slower of two batch dimensions (0 with fewer)
+    explicit Layout(const Problem &P) {
+        const size_t nb = P.b.size();
+        rows = P.xs == 1 && P.ys == 1 && nb <= 1;
+        pitch_in = nb ? P.b[0].sin : P.xlen; pitch_out = nb ? P.b[0].sout : P.ylen;
+        dense = rows && pitch_in == P.xlen && pitch_out == P.ylen;
+        cols = nb && P.b.back().sin == 1 && P.b.back().sout == 1;
+        inner = nb ? P.b.back().shape : 1;
+        lane_in = nb ? P.b.back().sin : 0; lane_out = nb ? P.b.back().sout : 0;
+        outer_in = nb == 2 ? P.b[0].sin : 0; outer_out = nb == 2 ? P.b[0].sout : 0;
+    }
+};
 
 // A route (of dispatch() in exec.hip, of ndfft_exec in host.hip) returns NDFFT_OK, a real error (returned to the caller), or kDeclined:
 // "not mine, the next route runs".  kDeclined is no ndfft status and never leaves the function that walks the routes.
@@ -126,7 +159,7 @@ struct MallModel {
 };
 struct DeviceWs {
     MallModel mall;
-    std::map<hipStream_t, Scratch> scratch[9];   // 0..7: the multi-pass routes; 8: the image a weight pass writes ahead of the transform (exec.hip: weighted)
+    std::map<hipStream_t, Scratch> scratch[9];   // 0..7: the multi-pass routes; 8: the image a weight pass writes ahead of the transform (compose.hip: weighted, filter_composed)
     Staging stage_in, stage_out;
     PinnedBuf bounce_in[3], bounce_out[3];
     Pipe pipe;

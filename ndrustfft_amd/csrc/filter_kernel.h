@@ -6,9 +6,9 @@
 // same way, rader_kernel.h).  The inverse's last pass then stores in the forward's load pattern.  IFFT(y) = conj(FFT(conj(y))): both pass sets are forward ones.
 //
 // The struct is two Pow2Kernel instantiations over the same (T, N, TPL, LPB, HALF, FLAGS, NT, VEC) and uses their passes<0> only.  Instantiated and launched
-// from kernels_pow2.hip (launch_filter_pow2).
+// from kernels_filter.hip (launch_filter).
 //
-// REAL: the same on a REAL lane of n = 2N points under an R2C plan (launch_filter_r2c_pow2): out = s IRFFT(w (.) RFFT(in)), w of N + 1 complex values.  The lane is
+// REAL: the same on a REAL lane of n = 2N points under an R2C plan (MODE = FILTER_R2C): out = s IRFFT(w (.) RFFT(in)), w of N + 1 complex values.  The lane is
 // read as N complex points z[m] = x[2m] + i x[2m+1] -- the load and the store are the complex kernel's, each complex element two adjacent reals -- and only the step
 // between the two pass sets differs: the half spectrum X[k], X[N-k] of the real lane needs Z[k] AND Z[N-k], which another thread holds, so the lane goes through
 // its LDS once more (write Z, barrier, gather the mirror bin; the components one after the other where the exchange buffer holds one), and every thread then
@@ -18,7 +18,7 @@
 // The unnormalised inverse FFT_N of Z' is y[2m] + i y[2m+1] with y = n irfft(w (.) rfft(x)).  Both bins of a pair are computed by both threads that hold one of
 // them: twice the arithmetic of the split, no second exchange.
 //
-// FILTER_DCT: the same on a REAL lane of n = 2N points under a DCT plan (launch_filter_dct_pow2): out = s DCT3(g (.) DCT2(in)), g of n REAL values, both transforms the
+// FILTER_DCT: the same on a REAL lane of n = 2N points under a DCT plan (MODE = FILTER_DCT): out = s DCT3(g (.) DCT2(in)), g of n REAL values, both transforms the
 // unnormalised lane definitions C[k] = sum_j x[j] cos(pi (2j+1) k / (2n)),  y[j] = D[0] / 2 + sum_{k>=1} D[k] cos(pi (2j+1) k / (2n))  (Makhoul; realops.h G_DCT2_EVEN,
 // G_DCT3_EVEN).  With v[m] = x[2m], v[n-1-m] = x[2m+1] and V = RFFT_n(v), C[k] = Re(c_k V[k]), C[n-k] = -Im(c_k V[k]), c_k = e^{-i pi k/(2n)}; backwards
 // V'[k] = conj(c_k) (D[k] - i D[n-k]) / 2 (D[n] := 0), v' = n irfft(V'), y[2m] = v'[m], y[2m+1] = v'[n-1-m].  The kernel:
@@ -32,6 +32,7 @@
 //   store    z' = y[4m] + i y[4m+2] / y[2n-1-4m] + i y[2n-3-4m]: the load's map backwards through the LDS, contiguous global stores.  Dead tail lanes take part in
 //            every staging barrier and store nothing; every load of a workgroup precedes its first barrier, so a call in place is safe.
 #pragma once
+#include <type_traits>
 #include "pow2_kernel.h"
 #include "realops.h"
 
@@ -87,8 +88,7 @@ template <typename T, int N, int VEC> constexpr int filter_mix_split_dct() {
     return N == 64 || N == 256 || N == 1024 || (N == 2048 && VEC == 1) ? 8 : 0;
 }
 
-// MODE (a bool before the DCT form: false / true still name the first two)
-enum { FILTER_C2C = 0, FILTER_R2C = 1, FILTER_DCT = 2 };
+// MODE: FILTER_C2C / FILTER_R2C / FILTER_DCT of engine.h (a bool before the DCT form: false / true still name the first two)
 // FILTER_DCT: VEC is the number of REALS per global access (1, or 16 / sizeof(T)); the pass sets always own butterflies j = t + q TPL
 template <typename T, int V> struct real_vec { typedef T type __attribute__((ext_vector_type(V))); };
 
@@ -164,6 +164,25 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
     }
     static_assert((FLAGS & ~16) == 0, "product flags other than the derived twiddle powers have no meaning here");
 
+    // The steps between the two pass sets as functions of VALUES: a helper that takes the register arrays by reference moved the registers or the schedule of some
+    // instance (profiles/r14/isa_diff.txt), so the loops over the registers, the loads, the stores and the DCT mix stay in run().
+    // after the first pass set v[q RZ + r] of thread t is bin bin(t, q, r) of the lane's spectrum (the last pass's output index, pow2_kernel.h)
+    static __device__ __forceinline__ int bin(int t, int q, int r) { return KF::template jof<NP - 1>(t, q) + r * NBZ; }
+    // the pair split.  A = Z[k], B = conj Z[(N-k) mod N]:  e = (A + B) / 2,  o = W (A - B) / (2i)
+    static __device__ __forceinline__ cpx<T> split_even(const cpx<T> A, const cpx<T> B) { return mk<T>((A.x + B.x) * (T)0.5, (A.y + B.y) * (T)0.5); }
+    static __device__ __forceinline__ cpx<T> split_odd(const cpx<T> A, const cpx<T> B, const cpx<T> W) { return cmul(mk<T>((A.y - B.y) * (T)0.5, -(A.x - B.x) * (T)0.5), W); }
+    // One bin's step: A = Z[k] in, conj(Z'[k]) out (the inverse runs forward passes); zm = Z[(N - k) mod N] from the mirror exchange.  The tables are read with the
+    // default cache policy: every lane reads the same vectors.
+    // C2C: the bin times its weight
+    static __device__ __forceinline__ cpx<T> mix_c2c(const cpx<T> A, int k, const cpx<T> *w) { return cconj(cmul(A, w[k])); }
+    // R2C pair mix (the formulas at the top; r2c_split_pair and herm_fold of realops.h on registers).  w: N + 1 values; wn[k] = W_n^k, k <= N
+    static __device__ __forceinline__ cpx<T> mix_r2c(const cpx<T> A, const cpx<T> zm, int k, const cpx<T> *w, const cpx<T> *wn) {
+        const cpx<T> W = wn[k], B = cconj(zm), e = split_even(A, B), o = split_odd(A, B, W);
+        cpx<T> yk = cmul(w[k], cadd(e, o)), ym = cmul(w[N - k], cconj(csub(e, o)));
+        if (k == 0) { yk.y = (T)0; ym.y = (T)0; }
+        return herm_fold<T>(yk, cconj(ym), W);
+    }
+
     static __device__ __forceinline__ void run(const FilterArgs &f) {
         extern __shared__ __attribute__((aligned(16))) char smem[];
         const Pow2Args &a = f.a;
@@ -205,47 +224,37 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
                 for (int r = 0; r < R0; ++r) v[q * R0 + r] = gload<T, (NT & 2) != 0>(in + t + q * TPL + r * NB0);
         }
         KF::template passes<0>(v, (const cpx<T> *)a.twp, lds, t);
-        // v[q RZ + r] is bin jof<NP-1>(t, q) + r NBZ: times its weight (default cache policy: every lane reads the same vector), conjugated for the inverse
+        // v[q RZ + r] is bin(t, q, r): mixed with its weight(s), conjugated for the inverse
         if constexpr (!MIRROR) {
             const cpx<T> *w = (const cpx<T> *)f.w;
 #pragma unroll
             for (int q = 0; q < NBFZ; ++q)
 #pragma unroll
-                for (int r = 0; r < RZ; ++r) v[q * RZ + r] = cconj(cmul(v[q * RZ + r], w[KF::template jof<NP - 1>(t, q) + r * NBZ]));
+                for (int r = 0; r < RZ; ++r) v[q * RZ + r] = mix_c2c(v[q * RZ + r], bin(t, q, r), w);
         } else {
-            // mirror exchange: b[i] = Z[(N - k) mod N] for the bin k of v[i].  The barrier in front of a write: no thread still reads what the write replaces (the last
-            // exchange of the first pass set, the other component's round); dead tail lanes take part in every barrier
+            // mirror exchange: b[i] = Z[(N - k) mod N] for the bin k of v[i], through the lane's LDS: whole elements in one round, or the components one after the other
+            // where the exchange buffer holds one (HALF).  The barrier in front of a write: no thread still reads what the write replaces (the last exchange of the
+            // first pass set, the other component's round); dead tail lanes take part in every barrier
             cpx<T> b[E];
-            if constexpr (HALF) {
-                T *s = (T *)lds;
+            using S = typename std::conditional<HALF, T, cpx<T>>::type;      // what one round moves
+            S *s = (S *)lds;
 #pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    __syncthreads();
-#pragma unroll
-                    for (int q = 0; q < NBFZ; ++q)
-#pragma unroll
-                        for (int r = 0; r < RZ; ++r) s[phi(KF::template jof<NP - 1>(t, q) + r * NBZ)] = half ? v[q * RZ + r].y : v[q * RZ + r].x;
-                    __syncthreads();
-#pragma unroll
-                    for (int q = 0; q < NBFZ; ++q)
-#pragma unroll
-                        for (int r = 0; r < RZ; ++r) {
-                            const T x = s[phi((N - (KF::template jof<NP - 1>(t, q) + r * NBZ)) & (N - 1))];
-                            if (half) b[q * RZ + r].y = x; else b[q * RZ + r].x = x;
-                        }
-                }
-            } else {
-                cpx<T> *s = (cpx<T> *)lds;
+            for (int half = 0; half < (HALF ? 2 : 1); ++half) {
                 __syncthreads();
 #pragma unroll
                 for (int q = 0; q < NBFZ; ++q)
 #pragma unroll
-                    for (int r = 0; r < RZ; ++r) s[phi(KF::template jof<NP - 1>(t, q) + r * NBZ)] = v[q * RZ + r];
+                    for (int r = 0; r < RZ; ++r) {
+                        if constexpr (HALF) s[phi(bin(t, q, r))] = half ? v[q * RZ + r].y : v[q * RZ + r].x; else s[phi(bin(t, q, r))] = v[q * RZ + r];
+                    }
                 __syncthreads();
 #pragma unroll
                 for (int q = 0; q < NBFZ; ++q)
 #pragma unroll
-                    for (int r = 0; r < RZ; ++r) b[q * RZ + r] = s[phi((N - (KF::template jof<NP - 1>(t, q) + r * NBZ)) & (N - 1))];
+                    for (int r = 0; r < RZ; ++r) {
+                        const S x = s[phi((N - bin(t, q, r)) & (N - 1))];
+                        if constexpr (HALF) { if (half) b[q * RZ + r].y = x; else b[q * RZ + r].x = x; } else b[q * RZ + r] = x;
+                    }
             }
             if constexpr (DCT) {
                 // pair mix (the formulas at the top).  g: 2 N reals, c[k] = e^{-i pi k/(4N)}, k < 2 N, wn[k] = W_n^k, k <= N: default cache policy, every lane reads the same
@@ -256,10 +265,9 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
                 for (int q = 0; q < NBFZ; ++q)
 #pragma unroll
                     for (int r = 0; r < RZ; ++r) {
-                        const int k = KF::template jof<NP - 1>(t, q) + r * NBZ;
+                        const int k = bin(t, q, r);
                         const cpx<T> A = v[q * RZ + r], B = cconj(b[q * RZ + r]), W = wn[k], ck = c[k], cm = c[N - k];
-                        const cpx<T> e = mk<T>((A.x + B.x) * hf, (A.y + B.y) * hf);
-                        const cpx<T> o = cmul(mk<T>((A.y - B.y) * hf, -(A.x - B.x) * hf), W);
+                        const cpx<T> e = split_even(A, B), o = split_odd(A, B, W);
                         const cpx<T> tk = cmul(ck, cadd(e, o)), tm = cmul(cm, cconj(csub(e, o)));                  // c_k V[k], c_{N-k} V[N-k]
                         const T dk = hf * g[k] * tk.x, dm = hf * g[N - k] * tm.x;                                    // D[k] / 2, D[N-k] / 2
                         const T dnk = k ? -hf * g[(2 * N - k) & (2 * N - 1)] * tk.y : (T)0, dpk = k ? -hf * g[N + k] * tm.y : dm;     // D[n-k] / 2 (D[n] := 0; g has no element n), D[N+k] / 2 (k = 0: D[N] once)
@@ -268,21 +276,14 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
                         if constexpr (MIX_SPLIT > 0) { if ((r + 1) % (RZ / MIX_SPLIT) == 0) mix_fence(); }
                     }
             } else {
-            // pair mix (the formulas at the top; r2c_split_pair and herm_fold of realops.h on registers).  w: N + 1 values, default cache policy; wn[k] = W_n^k, k <= N
-            const cpx<T> *w = (const cpx<T> *)f.w, *wn = (const cpx<T> *)f.wn;
+                const cpx<T> *w = (const cpx<T> *)f.w, *wn = (const cpx<T> *)f.wn;
 #pragma unroll
-            for (int q = 0; q < NBFZ; ++q)
+                for (int q = 0; q < NBFZ; ++q)
 #pragma unroll
-                for (int r = 0; r < RZ; ++r) {
-                    const int k = KF::template jof<NP - 1>(t, q) + r * NBZ;
-                    const cpx<T> A = v[q * RZ + r], B = cconj(b[q * RZ + r]), W = wn[k];
-                    const cpx<T> e = mk<T>((A.x + B.x) * (T)0.5, (A.y + B.y) * (T)0.5);
-                    const cpx<T> o = cmul(mk<T>((A.y - B.y) * (T)0.5, -(A.x - B.x) * (T)0.5), W);
-                    cpx<T> yk = cmul(w[k], cadd(e, o)), ym = cmul(w[N - k], cconj(csub(e, o)));
-                    if (k == 0) { yk.y = (T)0; ym.y = (T)0; }
-                    v[q * RZ + r] = herm_fold<T>(yk, cconj(ym), W);      // conj(Z'[k]): the inverse runs forward passes
-                    if constexpr (MIX_SPLIT > 0) { if ((r + 1) % (RZ / MIX_SPLIT) == 0) mix_fence(); }
-                }
+                    for (int r = 0; r < RZ; ++r) {
+                        v[q * RZ + r] = mix_r2c(v[q * RZ + r], b[q * RZ + r], bin(t, q, r), w, wn);
+                        if constexpr (MIX_SPLIT > 0) { if ((r + 1) % (RZ / MIX_SPLIT) == 0) mix_fence(); }
+                    }
             }
         }
         // (the first exchange of the second pass set starts with a barrier: no thread overwrites LDS another still reads from the first set's last exchange, or gathers from)

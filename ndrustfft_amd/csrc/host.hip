@@ -1,7 +1,7 @@
 // host.hip -- ndfft_exec: one nd* call on the caller's own host arrays, the only call the reference's signature can make (src/lib.rs:105-115).
 // The arrays are staged through HBM by one of four strategies, tried in order (the routes at the end of this file): mapped bounce buffers
 // for small calls, a chunk pipeline straight on pinned / registered arrays, the same pipeline through pinned bounce buffers for pageable
-// ones, plain synchronous copies.  Validation and kernel choice are exec.hip's (prepare, dispatch_peeled: exec_internal.h);
+// ones, plain synchronous copies.  Validation and kernel choice are exec.hip's (prepare, dispatch), reached through compose.hip's dispatch_peeled (exec_internal.h);
 // docs/host_path.md has the map.
 #include <algorithm>
 #include <atomic>

@@ -24,7 +24,6 @@
 #include <cstdlib>
 
 #include "pow2_config.h"
-#include "filter_kernel.h"
 
 namespace ndfft {
 
@@ -108,14 +107,7 @@ template <typename T, int N, int NT, int VEC, int FL = 0> static int launch_one(
     return launch_inst<T, N, 1, VEC, FL>(a, s);
 }
 
-// f32: 16-byte (two-element) accesses where the configuration allows them (an even number of butterflies per
-// thread in the first and last pass) and the lanes are 16-byte aligned; n = 64 runs 8 threads x 8 elements with
-// 8-byte accesses (measured 92 us vs 106 us for 4 x 16 with 16-byte accesses on 2^25 points)
-template <int N> static constexpr bool f32_can_vec2() {
-    using RL = typename Pow2Cfg<float, N>::RL;
-    constexpr int E = N / Pow2Cfg<float, N>::TPL;
-    return (E / RL::at(0)) % 2 == 0 && (E / RL::at(RL::NP - 1)) % 2 == 0;
-}
+// f32: 16-byte (two-element) accesses where the configuration allows them (pow2_config.h: f32_can_vec2) and the lanes are 16-byte aligned
 template <int N> static int launch_f32(bool vec_ok, bool fused, const Pow2Args &a, hipStream_t s) {
     if constexpr (f32_can_vec2<N>()) {
         if (vec_ok) return fused ? launch_one<float, N, 1, 2, 8>(a, s) : launch_one<float, N, 1, 2>(a, s);
@@ -144,129 +136,10 @@ int launch_pow2(int dtype, int n, const Pow2Args &a, hipStream_t s) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// ndfft_filter, fused (filter_kernel.h): FFT, weights and inverse FFT of a lane in one launch.  n = 64 .. 4096; the two longest lengths (PSPLIT forms, 122-126
-// VGPRs for one pass set) stay on the composed route of exec.hip.  Same XCD map, load policy and 16-byte rule for f32 as launch_pow2 above.
-// ---------------------------------------------------------------------------------------------
-static constexpr int kFilterMaxN = 4096;
-bool filter_pow2_supported(int dtype, int n) { return n <= kFilterMaxN && pow2_supported(dtype, n); }
-// per-pass twiddles of the reversed radix list; empty when the list is a palindrome (the plan's own table serves both pass sets)
-void filter_pow2_build_twiddles(int dtype, int n, HostTable &out) {
-    switch (n) {
-#define NDFFT_CASE(N_, TPL_, ...)                                                                                                         \
-    case N_:                                                                                                                              \
-        if (dtype == NDFFT_F32) { if (!radix_palindromic<Pow2Cfg<float, N_>::RL>()) build_tw<Reversed<Pow2Cfg<float, N_>::RL>::type>(out); } \
-        else if (!radix_palindromic<Pow2Cfg<double, N_>::RL>()) build_tw<Reversed<Pow2Cfg<double, N_>::RL>::type>(out);                    \
-        break;
-        NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
-#undef NDFFT_CASE
-        default: break;
-    }
-}
-template <typename T, int N, int NT, int VEC, int MODE = FILTER_C2C> static int launch_filter_inst(const FilterArgs &f0, hipStream_t s) {
-    constexpr int TPL = Pow2Cfg<T, N>::TPL, LPB = lpb_for(TPL);
-    using K = FilterKernel<T, N, TPL, LPB, Pow2Half<T, N>::value, typename Pow2Cfg<T, N>::RL, N >= 4096 ? 16 : 0, NT, VEC, MODE>;
-    NDFFT_ENSURE_LDS_ATTR((k_filter_pow2<K>));
-    const int64_t nblk = (f0.a.nlanes + LPB - 1) / LPB;
-    if (nblk <= 0) return NDFFT_OK;
-    if (nblk > 0x7fffffffLL) return fail(NDFFT_ERR_UNSUPPORTED, "too many lanes for one launch");
-    FilterArgs f = f0;
-    f.a.xcd_chunk = xcd_chunk_for((size_t)LPB * N * sizeof(cpx<T>), nblk);
-    hipLaunchKernelGGL(k_filter_pow2<K>, dim3((unsigned)nblk), dim3(K::THREADS), K::LDS_BYTES, s, f);
-    NDFFT_HIP(hipGetLastError());
-    return NDFFT_OK;
-}
-template <typename T, int N, int VEC, int MODE = FILTER_C2C> static int launch_filter_one(const FilterArgs &f, hipStream_t s) {
-    const bool nt_in = f.a.stream_in >= 0 ? f.a.stream_in != 0 : stream_loads_for((size_t)f.a.nlanes * N * sizeof(cpx<T>));
-    return nt_in ? launch_filter_inst<T, N, 3, VEC, MODE>(f, s) : launch_filter_inst<T, N, 1, VEC, MODE>(f, s);
-}
-template <int N> static int launch_filter_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
-    if constexpr (N <= kFilterMaxN) {
-        if (dtype == NDFFT_F64) return launch_filter_one<double, N, 1>(f, s);
-        if constexpr (f32_can_vec2<N>()) { if (vec_ok) return launch_filter_one<float, N, 2>(f, s); }
-        return launch_filter_one<float, N, 1>(f, s);
-    } else {
-        return fail(NDFFT_ERR_UNSUPPORTED, "filter kernel: unsupported n");
-    }
-}
-int launch_filter_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s) {
-    const Pow2Args &a = f.a;
-    const bool vec_ok = a.pitch_in % 2 == 0 && a.pitch_out % 2 == 0 && ((uintptr_t)a.in % 16) == 0 && ((uintptr_t)a.out % 16) == 0;
-    switch (n) {
-#define NDFFT_CASE(N_, TPL_, ...) case N_: return launch_filter_n<N_>(dtype, vec_ok, f, s);
-        NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
-#undef NDFFT_CASE
-        default: return fail(NDFFT_ERR_UNSUPPORTED, "filter kernel: unsupported n");
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// ... and on REAL lanes of n = 2 F points under an R2C plan (filter_kernel.h: REAL): the complex kernel of length F with the mirror exchange and the pair mix between its
-// two pass sets.  F = 64 .. 4096, the lengths instantiated above, i.e. n = 128 .. 8192; kFilterR2cN is THE list of shipped instances (tests/filter_real_suite.py: FUSED_R_N
-// mirrors it): every one measured 53-67 % below the composed route.
-// The caller passes pitches in COMPLEX elements (half the real pitches) and bases that are whole complex elements.
-// ---------------------------------------------------------------------------------------------
-static constexpr int kFilterR2cN[] = {128, 256, 512, 1024, 2048, 4096, 8192};
-bool filter_r2c_pow2_supported(int dtype, int n) {
-    (void)dtype;
-    for (int m : kFilterR2cN) if (m == n) return filter_pow2_supported(dtype, n / 2);
-    return false;
-}
-// per-pass twiddles of the length-F list and of its reverse (empty: a palindrome), F = n / 2
-void filter_r2c_build_twiddles(int dtype, int n, HostTable &fwd, HostTable &rev) {
-    pow2_build_twiddles(dtype, n / 2, fwd);
-    filter_pow2_build_twiddles(dtype, n / 2, rev);
-}
-template <int N> static int launch_filter_r2c_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
-    if constexpr (N <= kFilterMaxN) {
-        if (dtype == NDFFT_F64) return launch_filter_one<double, N, 1, FILTER_R2C>(f, s);
-        if constexpr (f32_can_vec2<N>()) { if (vec_ok) return launch_filter_one<float, N, 2, FILTER_R2C>(f, s); }
-        return launch_filter_one<float, N, 1, FILTER_R2C>(f, s);
-    } else {
-        return fail(NDFFT_ERR_UNSUPPORTED, "real filter kernel: unsupported n");
-    }
-}
-int launch_filter_r2c_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s) {
-    const Pow2Args &a = f.a;
-    if (!filter_r2c_pow2_supported(dtype, n)) return fail(NDFFT_ERR_UNSUPPORTED, "real filter kernel: unsupported n");
-    const bool vec_ok = a.pitch_in % 2 == 0 && a.pitch_out % 2 == 0 && ((uintptr_t)a.in % 16) == 0 && ((uintptr_t)a.out % 16) == 0;
-    switch (n / 2) {
-#define NDFFT_CASE(N_, TPL_, ...) case N_: return launch_filter_r2c_n<N_>(dtype, vec_ok, f, s);
-        NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
-#undef NDFFT_CASE
-        default: return fail(NDFFT_ERR_UNSUPPORTED, "real filter kernel: unsupported n");
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// ... and on REAL lanes of n = 2 F points under a DCT plan (filter_kernel.h: FILTER_DCT): DCT-II, n real weights, DCT-III.  The same complex kernel of length F between a
-// staged load through Makhoul's permutation and a staged store through its inverse.  kFilterDctN is THE list of shipped instances (tests/filter_dct_suite.py: FUSED_D_N
-// mirrors it).  Pitches in REALS; any base and any pitch: the accesses are sizeof(T) wide unless both sides are 16-byte aligned (bases and pitches), then 16 bytes.
-// ---------------------------------------------------------------------------------------------
-static constexpr int kFilterDctN[] = {128, 256, 512, 1024, 2048, 4096, 8192};
-bool filter_dct_pow2_supported(int dtype, int n) {
-    for (int m : kFilterDctN) if (m == n) return filter_pow2_supported(dtype, n / 2);
-    return false;
-}
-template <int N> static int launch_filter_dct_n(int dtype, bool vec_ok, const FilterArgs &f, hipStream_t s) {
-    if constexpr (N <= kFilterMaxN) {
-        if (dtype == NDFFT_F64) return vec_ok ? launch_filter_one<double, N, 2, FILTER_DCT>(f, s) : launch_filter_one<double, N, 1, FILTER_DCT>(f, s);
-        return vec_ok ? launch_filter_one<float, N, 4, FILTER_DCT>(f, s) : launch_filter_one<float, N, 1, FILTER_DCT>(f, s);
-    } else {
-        return fail(NDFFT_ERR_UNSUPPORTED, "dct filter kernel: unsupported n");
-    }
-}
-int launch_filter_dct_pow2(int dtype, int n, const FilterArgs &f, hipStream_t s) {
-    const Pow2Args &a = f.a;
-    if (!filter_dct_pow2_supported(dtype, n)) return fail(NDFFT_ERR_UNSUPPORTED, "dct filter kernel: unsupported n");
-    const int64_t per16 = dtype == NDFFT_F64 ? 2 : 4;
-    const bool vec_ok = a.pitch_in % per16 == 0 && a.pitch_out % per16 == 0 && ((uintptr_t)a.in % 16) == 0 && ((uintptr_t)a.out % 16) == 0;
-    switch (n / 2) {
-#define NDFFT_CASE(N_, TPL_, ...) case N_: return launch_filter_dct_n<N_>(dtype, vec_ok, f, s);
-        NDFFT_POW2_CONFIGS_F64(NDFFT_CASE)
-#undef NDFFT_CASE
-        default: return fail(NDFFT_ERR_UNSUPPORTED, "dct filter kernel: unsupported n");
-    }
-}
-
 }  // namespace ndfft
+
+// kernels_filter.hip is a unit of its own (-DNDFFT_FILTER_UNIT, set by every build list that names it).  A list of objects written before it existed expects
+// the filter launchers here: such a build gets them through this unit.
+#ifndef NDFFT_FILTER_UNIT
+#include "kernels_filter.hip"
+#endif

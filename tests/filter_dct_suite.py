@@ -1,6 +1,6 @@
 """Cases of nddct_filter on device arrays under a DctHandler: ndfft_exec_dct_filter_device (include/ndfft_mi355x_ext.h) driven through ctypes with devmem's helpers,
 so that the same functions run on the CPU build of the kernel sources (tests/test_filter_dct_emul.py) and on the MI355X (tests/test_filter_dct_gpu.py).  The fused
-route filter_dct_pow2 (filter_kernel.h: FILTER_DCT; exec.hip: filter_fused) and the calls that must stay on the composed route.
+route filter_dct_pow2 (filter_kernel.h: FILTER_DCT; compose.hip: filter_fused) and the calls that must stay on the composed route.
 
 Expected values: the CPU oracle composed, nddct2 -> `*= g` in the working dtype -> nddct3 under the same normalisation; coarse bound helpers.TOL.  Working
 precision: the bar of docs/accuracy.md, truth = scipy.fft.dct of type 2 and 3 one precision up, rescaled to the library's lane definitions
@@ -22,7 +22,7 @@ from weights_suite import make_weights
 BOTH = (np.float64, np.float32)
 NO_FUSE = _lib.FILTER_NO_FUSE
 FUSED_D = "filter_dct_pow2"
-FUSED_D_N = (128, 256, 512, 1024, 2048, 4096, 8192)          # kernels_pow2.hip: kFilterDctN
+FUSED_D_N = (128, 256, 512, 1024, 2048, 4096, 8192)          # kernels_filter.hip: NDFFT_FILTER_LENGTHS, as n = 2 F
 SCALE_OF = {_lib.NORM_NONE: 1.0, _lib.NORM_DEFAULT: 4.0}
 # (n = 2 F, the kernel is the complex one of length F: the radix lists of F = 128, 1024, 2048 in f64 and F = 2048 in f32 are no palindromes, so n = 256, 2048, 4096
 #  in f64 and n = 4096 in f32 run their second pass set on a second twiddle table -- weight_placement's lengths hold both kinds per dtype)

@@ -1,4 +1,4 @@
-"""Every compiled instance of the three fused filter kernels (filter_kernel.h: filter_pow2, filter_r2c_pow2, filter_dct_pow2).  kernels_pow2.hip picks one template
+"""Every compiled instance of the three fused filter kernels (filter_kernel.h: filter_pow2, filter_r2c_pow2, filter_dct_pow2).  kernels_filter.hip picks one template
 instantiation per call from the plan kind, the length, the dtype, the access width VEC (from base alignment and pitch) and the load policy NT (from the input hint, the
 residency model or NDFFT_STREAM_LOADS).  The three suites this one is built on (filter_suite, filter_real_suite, filter_dct_suite) run the wide, plain-load instance of
 every length and the narrow one at two lengths; here every (kind, length, dtype, VEC, NT) that ships is launched, named by its geometry and by ndfft_last_input_policy().
@@ -228,7 +228,7 @@ def defaults_in_force(L):
     policy_is(L, AUTO, "a small dense call after the cases that set a hint or NDFFT_STREAM_LOADS")
 
 
-# ---- 3. call shapes with code of their own in exec.hip: filter_fused ------------------------------------------------------------------------------------------
+# ---- 3. call shapes with code of their own in compose.hip: filter_fused ------------------------------------------------------------------------------------------
 def short_lengths(K):
     return (64, 128) if K is C2C else (128,)
 
@@ -282,7 +282,7 @@ def three_d_window(L, K, rdt):
 
 def six_d_stepped(L, K, rdt, n=128):
     """(2, 2, 2, 2, 2, n), stepped in every batch dim (the geometry of filter_suite.composed_c2c_layouts' last case at a fused length): five batch dims that do not merge,
-    one more than kMaxBatchDims, so filter_peeled peels the slowest on the host and every piece is composed.  filter_case: the skipped elements of the output keep the sentinel."""
+    one more than kMaxBatchDims, so the peel of compose.hip (peeled) takes the slowest off on the host and every piece is composed.  filter_case: the skipped elements of the output keep the sentinel."""
     shape, big = (2, 2, 2, 2, 2, n), (4, 4, 4, 4, 4, n)
     xa = np.zeros(big, K.elem(rdt))
     xv = xa[::2, ::2, ::2, ::2, ::2]

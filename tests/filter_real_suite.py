@@ -1,4 +1,4 @@
-"""Cases of ndfft_filter on REAL device arrays under an R2cFftHandler: the fused route filter_r2c_pow2 (filter_kernel.h: REAL; exec.hip: filter_fused) and the calls
+"""Cases of ndfft_filter on REAL device arrays under an R2cFftHandler: the fused route filter_r2c_pow2 (filter_kernel.h: REAL; compose.hip: filter_fused) and the calls
 that must stay on the composed route.  Built on tests/filter_suite.py's helpers -- filter_case(..., r2c=True) checks every call against the composed CPU oracle
 within helpers.TOL, every element of the output allocation outside the view, and the input allocation -- so that the same functions run on the CPU build of the
 kernel sources (tests/test_filter_real_emul.py) and on the MI355X (tests/test_filter_real_gpu.py)."""
@@ -13,7 +13,7 @@ from ndrustfft_amd import _lib
 from weights_suite import make_weights
 
 FUSED_R = "filter_r2c_pow2"
-FUSED_R_N = (128, 256, 512, 1024, 2048, 4096, 8192)          # kernels_pow2.hip: kFilterR2cN
+FUSED_R_N = (128, 256, 512, 1024, 2048, 4096, 8192)          # kernels_filter.hip: NDFFT_FILTER_LENGTHS, as n = 2 F
 # (n = 2 F, the kernel is the complex one of length F: the radix lists of F = 128, 1024, 2048 in f64 and F = 2048 in f32 are no palindromes, so n = 256, 2048, 4096
 #  in f64 and n = 4096 in f32 run their second pass set on a second twiddle table -- weight_placement's lengths hold all four)
 

@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ndrustfft_amd", "csrc")
 files = [os.path.abspath(a) for a in sys.argv[1:]] or sorted(glob.glob(os.path.join(SRC, "kernels_*.hip"))) + [os.path.join(SRC, f) for f in ("transpose.hip", "big.hip")]
 for f in files:
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "--cuda-device-only",
+    out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "--cuda-device-only", "-DNDFFT_FILTER_UNIT",   # (kernels_pow2.hip alone, not the filter unit it includes for older build lists)
                           "-c", f, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, cwd=SRC).stderr
     cur = None
     rows = []

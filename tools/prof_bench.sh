@@ -7,13 +7,13 @@ export TMPDIR=/tmp
 cd /tmp
 for PH in primary warm strong; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$PH -- python3 $GRAFT_REPO_ROOT/bench.py --steps 100 --warmup 10 --profile-phase $PH > $OUT/stats_$PH.log 2>&1
-  echo "stats $PH exit $?"
+  RC=$?; echo "stats $PH exit $RC"; [ $RC -eq 0 ] || exit $RC      # a failed run ends the script: nothing more is started on the GPU
   find $OUT/stats_$PH -name "*kernel_stats.csv" | head -1 | xargs -r -I{} cp {} $OUT/${PH}_kernel_stats.csv
   head -4 $OUT/${PH}_kernel_stats.csv | cut -c1-260
   if [ "$2" == "pmc" ]; then
     for C in FETCH_SIZE WRITE_SIZE; do
       timeout 900 rocprofv3 --pmc $C --output-format csv -d $OUT/pmc_${PH}_$C -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --ramp-ms 0 --profile-phase $PH > $OUT/pmc_${PH}_$C.log 2>&1
-      echo "pmc $PH $C exit $?"
+      RC=$?; echo "pmc $PH $C exit $RC"; [ $RC -eq 0 ] || exit $RC
     done
   fi
 done
