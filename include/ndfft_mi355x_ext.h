@@ -60,6 +60,11 @@ int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in,
  *                                      both arrays, lanes at a uniform pitch): ONE kernel, one read and one write of device memory per point, no scratch memory.
  *                                      Nothing is allocated except, at the first call of a plan whose radix list is no palindrome (f64 128, 1024, 2048; f32 2048), a
  *                                      second twiddle table: every other length can be captured into a HIP graph without a warm-up call.
+ *   "filter_col_pow2"                  C2C plan, n = 128 .. 2048 a power of two, along a STRIDED axis: the fastest batch dimension has unit stride in both arrays
+ *                                      (neighbouring lanes are adjacent: axis 0 of a 2-D C-layout array, the middle axis of a 3-D one, windows of either; the
+ *                                      axis strides of the two arrays may differ), at least 8 lanes along it, at most two batch dimensions after merging: ONE
+ *                                      kernel, a workgroup per tile of 4 .. 32 adjacent lanes staged through LDS, one read and one write of device memory per point,
+ *                                      no scratch memory.  Allocates what "filter_pow2" allocates.
  *   "filter_r2c_pow2"                  R2C plan, n = 128 .. 8192 a power of two, unit stride along the axis in both arrays, lanes at a uniform pitch, both base
  *                                      pointers multiples of 2 * sizeof(T) and both lane pitches even (every lane starts on a whole complex element): ONE kernel
  *                                      on the real lane read as n / 2 complex points, one read and one write of device memory per real point, no scratch memory.

@@ -490,7 +490,9 @@ NDRUSTFFT_DEFINE(nddct4, T, T, DctHandler, NDFFT_OP_DCT4, T, true, true)        
 // ---- ndfft_filter: output = IFFT(weights (.) FFT(input)) along `axis` in one call (ndfft_exec_filter_device, include/ndfft_mi355x_ext.h) --------------------
 // What ndfft -> `lane *= weights` -> ndifft (FftHandler; n complex weights) or ndfft_r2c -> multiply -> ndifft_r2c (R2cFftHandler; real arrays, n / 2 + 1 complex
 // weights) give under the handler's normalisation, which must be None or Default.  Unit-stride power-of-two lanes run one fused kernel: complex lanes of
-// 64 .. 4096 points (ndfft_last_path() == "filter_pow2") and real lanes of 128 .. 8192 points that start on even element offsets ("filter_r2c_pow2"); everything
+// 64 .. 4096 points (ndfft_last_path() == "filter_pow2") and real lanes of 128 .. 8192 points that start on even element offsets ("filter_r2c_pow2"); complex lanes
+// of 128 .. 2048 points along a strided axis whose neighbouring lanes are adjacent in both arrays (axis 0 of a 2-D array, the middle axis of a 3-D one; at least
+// 8 adjacent lanes) run one fused kernel of column tiles ("filter_col_pow2"); everything
 // else runs transform + diagonal pass + transform, and fuse = false forces that form.  `&input == &output` is the in-place filter.
 // Asynchronous on the default stream, like the other DeviceArray calls.  Asynchronous on the default stream, like the other DeviceArray calls.
 namespace detail {

@@ -228,7 +228,9 @@ def ndfft_filter(input, output, handler, axis, weights, *, fuse=True):
     meaning ndfft_r2c -> multiply -> ndifft_r2c).  `input is output` is the in-place filter.
 
     torch tensors on the GPU go to ndfft_exec_filter_device (asynchronous on the current stream): one fused kernel for unit-stride power-of-two lanes -- complex
-    lanes of 64 .. 4096 points (path "filter_pow2"), real lanes of 128 .. 8192 points that start on even element offsets ("filter_r2c_pow2") -- and transform +
+    lanes of 64 .. 4096 points (path "filter_pow2"), real lanes of 128 .. 8192 points that start on even element offsets ("filter_r2c_pow2") --, one fused
+    kernel of column tiles for complex lanes of 128 .. 2048 points along a strided axis whose neighbouring lanes are adjacent in both arrays (axis 0 of a 2-D
+    C-layout array, the middle axis of a 3-D one, windows of either; at least 8 adjacent lanes, at most two batch dims; path "filter_col_pow2"), and transform +
     diagonal pass + transform otherwise (fuse=False forces that form).  `weights` is then a device tensor of the handler's complex dtype, or a
     numpy array that is uploaded once per call.  numpy arrays run the three steps through the host calls."""
     if not isinstance(handler, (FftHandler, R2cFftHandler)):

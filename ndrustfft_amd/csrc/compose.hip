@@ -140,6 +140,26 @@ static const FilterMode kFilterDct = {
     any_lanes,
     [](const ndfft_plan *plan, FilterArgs &f) { return get_filter_r2c_tables(plan, &f.a.twp, &f.twp_rev, &f.wn, &f.c); }};
 
+// fused, C2C along a strided axis: the fastest batch dim has unit stride in both views (axis 0 of a 2-D C-layout array, the middle axis of a 3-D one, windows of
+// either), at most two batch dims, at least 8 adjacent lanes (the column engine's own rule, exec.hip: route_real_engine) and a length from 128 that has a column
+// instance -- one launch of column tiles, path filter_col_pow2.  Everything else stays composed.
+static int filter_fused_col(const FilterMode &m, const Problem &P, const Layout &L, const DevTables *dt, const char *d_in, char *d_out, const void *d_w, hipStream_t stream) {
+    const int dtype = P.plan->dtype, n = (int)P.plan->n;
+    if (!(L.cols && P.b.size() <= 2 && L.inner >= 8 && n >= 128 && filter_col_supported(dtype, n))) return kDeclined;
+    FilterArgs f;
+    f.a.in = d_in; f.a.out = d_out; f.a.nlanes = P.nlanes; f.a.pitch_in = f.a.pitch_out = 0;
+    f.a.inverse = 0; f.a.scale = P.scale; f.a.twp = dt->cfg[CFG_MAIN].twp;
+    f.w = d_w;
+    f.inner = L.inner; f.outer_in = L.outer_in; f.outer_out = L.outer_out; f.elem_in = P.xs; f.elem_out = P.ys;
+    int rc = m.tables(P.plan, f);
+    if (rc) return rc;
+    // a dense C-layout block: the whole array is read once and written once, as the row kernel's dense lanes are
+    const bool dense = P.xs == L.inner && P.ys == L.inner && (P.b.size() == 1 || (L.outer_in == n * L.inner && L.outer_out == n * L.inner));
+    if (dense) f.a.stream_in = c2c_row_load_policy(d_in, d_out, (size_t)P.nlanes * P.plan->n * m.array_reals * real_size(dtype));
+    set_last_path("filter_col_pow2");
+    return launch_filter_col(dtype, n, f, stream);
+}
+
 // fused: lanes of n = 64 .. 4096 complex points (128 .. 8192 reals) at unit stride along the axis and a uniform pitch, on which dispatch() would run pow2_reg in both
 // directions -- one launch, no scratch.  The first call of a plan builds and uploads the tables it lacks (get_filter_twiddles: none for a palindromic radix list;
 // get_filter_r2c_tables); later calls allocate nothing.
@@ -148,7 +168,9 @@ static int filter_fused(const FilterMode &m, const Problem &P, const char *d_in,
     int rc = get_dev_tables(P.plan, &dt);
     if (rc) return rc;
     const int dtype = P.plan->dtype, n = (int)P.plan->n;
-    if (!(Layout(P).rows && filter_supported(m.mode, dtype, n))) return kDeclined;
+    const Layout L(P);
+    if (!L.rows) return m.mode == FILTER_C2C ? filter_fused_col(m, P, L, dt, d_in, d_out, d_w, stream) : kDeclined;
+    if (!filter_supported(m.mode, dtype, n)) return kDeclined;
     // in reals or complex elements as the arrays have them (Layout's pitch_out is the half spectrum's for an R2C plan without a batch dim)
     int64_t pin = P.b.empty() ? n : P.b[0].sin, pout = P.b.empty() ? n : P.b[0].sout;
     const bool dense = pin == n && pout == n;

@@ -224,9 +224,15 @@ struct FilterArgs {
     const void *w;           // n complex weights, indexed by output bin of the forward transform (real lanes: n / 2 + 1)
     const void *wn = nullptr;   // real lanes only: W_n^k, k = 0 .. n / 2 (the R2C plan's aux1)
     const void *c = nullptr;    // DCT lanes only: e^{-i pi k/(2n)}, k < n (the DCT plan's aux2); w is then n REAL weights
+    // column form (launch_filter_col; the row launches leave these alone): lane L = (o, i) = (L / inner, L % inner), element j of it at o * outer_* + i + j * elem_*
+    // (adjacent lanes are adjacent in memory, as RealArgs has it); a.pitch_in / a.pitch_out are not read
+    int64_t inner = 0, outer_in = 0, outer_out = 0, elem_in = 0, elem_out = 0;
 };
 bool filter_supported(int mode, int dtype, int n);                   // n: the handler length (n = 64 .. 4096 complex points, 128 .. 8192 reals)
 int launch_filter(int mode, int dtype, int n, const FilterArgs &f, hipStream_t s);
+// the column form of FILTER_C2C (filter_kernel.h: FilterColKernel): one workgroup per tile of adjacent lanes
+bool filter_col_supported(int dtype, int n);
+int launch_filter_col(int dtype, int n, const FilterArgs &f, hipStream_t s);
 void filter_pow2_build_twiddles(int dtype, int n, HostTable &out);   // twiddles of the reversed radix list (empty: the list is a palindrome, the plan's table serves)
 void filter_r2c_build_twiddles(int dtype, int n, HostTable &fwd, HostTable &rev);   // real modes: per-pass twiddles of the length-n/2 list and of its reverse (empty: a palindrome)
 

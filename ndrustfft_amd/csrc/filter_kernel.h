@@ -6,7 +6,7 @@
 // same way, rader_kernel.h).  The inverse's last pass then stores in the forward's load pattern.  IFFT(y) = conj(FFT(conj(y))): both pass sets are forward ones.
 //
 // The struct is two Pow2Kernel instantiations over the same (T, N, TPL, LPB, HALF, FLAGS, NT, VEC) and uses their passes<0> only.  Instantiated and launched
-// from kernels_filter.hip (launch_filter).
+// from kernels_filter.hip (launch_filter).  FilterColKernel (below FilterKernel) is the same on a tile of ADJACENT lanes along a strided axis, staged through LDS (ColTile).
 //
 // REAL: the same on a REAL lane of n = 2N points under an R2C plan (MODE = FILTER_R2C): out = s IRFFT(w (.) RFFT(in)), w of N + 1 complex values.  The lane is
 // read as N complex points z[m] = x[2m] + i x[2m+1] -- the load and the store are the complex kernel's, each complex element two adjacent reals -- and only the step
@@ -323,6 +323,130 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
 #pragma unroll
                 for (int r = 0; r < R0; ++r) gstore<T, (NT & 1) != 0>(out + t + q * TPL + r * NB0, v[q * R0 + r]);
         }
+    }
+};
+
+// ---- column form: the transform axis is strided and ADJACENT LANES are contiguous (any axis but the last of a C-layout array) -----------------------------------
+// ColTile: a tile of LPB adjacent lanes x NE elements of type S between global memory and the workgroup's LDS, lanes fastest on the global side -- the staging of
+// RealPow2Kernel<..., COL = true> (pow2_real.h) on its own, so that the column forms of the real and cosine filters can use it with S = T.  Thread -> (cl = tid % LPB
+// fastest, row j0 = tid / LPB); rows j0, j0 + STEP, ... of the tile go to lane cl's slice of PITCH elements, PITCH odd: adjacent lanes fall on different banks.
+template <bool NT, typename S> __device__ __forceinline__ S tile_load(const S *p) {
+    if constexpr (!NT) return *p;
+    else if constexpr (std::is_same<S, cpx<double>>::value) return gload<double, true>(p);
+    else return __builtin_nontemporal_load(p);
+}
+template <bool NT, typename S> __device__ __forceinline__ void tile_store(S *p, S v) {
+    if constexpr (!NT) *p = v;
+    else if constexpr (std::is_same<S, cpx<double>>::value) gstore<double, true>(p, v);
+    else __builtin_nontemporal_store(v, p);
+}
+template <typename S, int NE, int LPB, int THREADS, int PITCH> struct ColTile {
+    static constexpr int STEP = THREADS / LPB, PER = NE / STEP;
+    static_assert(THREADS % LPB == 0 && NE % STEP == 0, "whole rows of the tile per round, whole rounds per lane");
+    static_assert(PITCH % 2 == 1 && PITCH >= NE, "an odd slice pitch that holds the lane");
+    static constexpr size_t LDS_BYTES = (size_t)LPB * PITCH * sizeof(S);
+    // this thread's lane in the load / store role: element 0 of it on both sides (in S), its slice; dead = past the last lane of a ragged last tile
+    struct Pos { int j0; bool live; int64_t in, out; S *slice; };
+    static __device__ __forceinline__ Pos pos(const FilterArgs &f, int64_t lane0, char *smem) {
+        Pos p;
+        const int cl = threadIdx.x % LPB;
+        p.j0 = threadIdx.x / LPB;
+        const int64_t L = lane0 + cl;
+        p.live = L < f.a.nlanes;
+        int64_t o, i;
+        if (f.a.nlanes <= 0x7fffffffLL) {      // (inner <= nlanes: both fit 32 bits, and a 64-bit division is about 60 VALU instructions per thread)
+            const uint32_t l = p.live ? (uint32_t)L : 0u, in = (uint32_t)f.inner;
+            o = l / in; i = l % in;
+        } else {
+            const int64_t l = p.live ? L : 0;
+            o = l / f.inner; i = l % f.inner;
+        }
+        p.in = o * f.outer_in + i; p.out = o * f.outer_out + i;
+        p.slice = (S *)smem + (size_t)cl * PITCH;
+        return p;
+    }
+    // every global load of the tile, into registers: nothing is stored to LDS, and no barrier passed, before the last one is issued
+    template <bool NT> static __device__ __forceinline__ void load(const Pos &p, const S *in, int64_t elem, S (&x)[PER]) {
+        if (p.live) {
+            const S *src = in + p.in + (int64_t)p.j0 * elem;
+#pragma unroll
+            for (int i = 0; i < PER; ++i) x[i] = tile_load<NT>(src + (int64_t)(i * STEP) * elem);
+        } else {
+#pragma unroll
+            for (int i = 0; i < PER; ++i) x[i] = S{};
+        }
+    }
+    static __device__ __forceinline__ void put(const Pos &p, const S (&x)[PER]) {
+#pragma unroll
+        for (int i = 0; i < PER; ++i) p.slice[p.j0 + i * STEP] = x[i];
+    }
+    // the tile back, lanes fastest; a dead lane stores nothing
+    template <bool NT> static __device__ __forceinline__ void store(const Pos &p, S *out, int64_t elem) {
+        if (!p.live) return;
+        S *dst = out + p.out + (int64_t)p.j0 * elem;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) tile_store<NT>(dst + (int64_t)(i * STEP) * elem, p.slice[p.j0 + i * STEP]);
+    }
+};
+
+// FilterColKernel: FilterKernel's FILTER_C2C on a column tile.  load (ColTile, every global load of the workgroup ahead of its first barrier: a tile is whole lanes and
+// tiles are disjoint, so a call in place is safe) | barrier | threads change role to (t = tid % TPL, ll = tid / TPL) and gather v[q R0 + r] = slice[jof<0>(t, q) + r N / R0]
+// | forward passes, mix_c2c, reversed passes, scale and conjugate as in the row form, the lane's slice the exchange buffer | barrier | scatter to the slice at
+// jof<NP-1> | barrier | store.  Dead lanes of a ragged last tile are zeros, take part in every barrier and store nothing.
+// HALF: the slice holds whole complex elements either way, so the component-wise exchange saves no LDS here, only doubles the exchange's barriers and LDS instructions;
+// the instances run whole elements (kernels_filter.hip), as the column transforms of pow2_real.h do.
+template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS, int NT, int MODE = FILTER_C2C> struct FilterColKernel {
+    static_assert(MODE == FILTER_C2C, "the column forms of the real and cosine filters are not written yet");
+    using RLR = typename Reversed<RL>::type;
+    using KF = Pow2Kernel<T, N, TPL, LPB, HALF, RL, FLAGS, 1, NT, 1>;
+    using KI = Pow2Kernel<T, N, TPL, LPB, HALF, RLR, FLAGS, 1, NT, 1>;
+    static constexpr int E = KF::E, THREADS = KF::THREADS, NP = RL::NP;
+    static constexpr int PITCH = (N + (N >> 4) + 2) | 1;      // RealPow2Kernel::LANE_LDS for COL
+    using Tile = ColTile<cpx<T>, N, LPB, THREADS, PITCH>;
+    static constexpr size_t LDS_BYTES = Tile::LDS_BYTES;
+    static constexpr int R0 = RL::at(0), NB0 = N / R0, NBF0 = KF::slots(0);
+    static constexpr int RZ = RL::at(NP - 1), NBZ = N / RZ, NBFZ = KF::slots(NP - 1);
+    static_assert(KI::E == E && E * TPL == N && Tile::PER == E && Tile::STEP == TPL, "both lists run whole butterfly rounds on the same registers; the load fills them once");
+    static_assert(KF::full(0) && KF::full(NP - 1), "whole rounds in the first and last pass");
+    static_assert(PITCH >= KF::LANE_LDS, "the slice is the lane's exchange buffer");
+    static_assert((FLAGS & ~16) == 0, "product flags other than the derived twiddle powers have no meaning here");
+
+    static __device__ __forceinline__ void run(const FilterArgs &f) {
+        extern __shared__ __attribute__((aligned(16))) char smem[];
+        const Pow2Args &a = f.a;
+        const int64_t lane0 = (int64_t)xcd_block(blockIdx.x, gridDim.x, a.xcd_chunk) * LPB;
+        const typename Tile::Pos p = Tile::pos(f, lane0, smem);
+        cpx<T> v[E];
+        Tile::template load<(NT & 2) != 0>(p, (const cpx<T> *)a.in, f.elem_in, v);
+        Tile::put(p, v);
+        __syncthreads();
+        const int t = threadIdx.x % TPL, ll = threadIdx.x / TPL;
+        cpx<T> *slice = (cpx<T> *)smem + (size_t)ll * PITCH;
+#pragma unroll
+        for (int q = 0; q < NBF0; ++q)
+#pragma unroll
+            for (int r = 0; r < R0; ++r) v[q * R0 + r] = slice[KF::template jof<0>(t, q) + r * NB0];
+        // (the first exchange of a pass set starts with a barrier: every gather above, and of the first set's last exchange, is done before a slice is overwritten)
+        KF::template passes<0>(v, (const cpx<T> *)a.twp, (char *)slice, t);
+        const cpx<T> *w = (const cpx<T> *)f.w;
+#pragma unroll
+        for (int q = 0; q < NBFZ; ++q)
+#pragma unroll
+            for (int r = 0; r < RZ; ++r) {
+                const int k = KF::template jof<NP - 1>(t, q) + r * NBZ;      // FilterKernel::bin
+                v[q * RZ + r] = cconj(cmul(v[q * RZ + r], w[k]));           // FilterKernel::mix_c2c
+            }
+        KI::template passes<0>(v, (const cpx<T> *)f.twp_rev, (char *)slice, t);
+        const T sc = (T)a.scale;
+#pragma unroll
+        for (int i = 0; i < E; ++i) { v[i].x *= sc; v[i].y *= -sc; }
+        __syncthreads();      // no thread still gathers from the second set's last exchange
+#pragma unroll
+        for (int q = 0; q < NBF0; ++q)
+#pragma unroll
+            for (int r = 0; r < R0; ++r) slice[KI::template jof<NP - 1>(t, q) + r * NB0] = v[q * R0 + r];
+        __syncthreads();
+        Tile::template store<(NT & 1) != 0>(p, (cpx<T> *)a.out, f.elem_out);
     }
 };
 

@@ -3,7 +3,8 @@
 
 Device-resident arrays, HBM-sourced over rotating (in, out) pairs whose inputs add up to at least 768 MiB (three times the Infinity Cache), timed with device
 events after a warm-up that also ramps the clock.  For c128 and c64 (an FftHandler), f64 and f32 (real arrays under an R2cFftHandler, n // 2 + 1 weights) or d64 and
-d32 (real arrays under a DctHandler: nddct_filter, n real weights; two_calls is nddct2 then nddct3) and the shapes 4096 x 4096, 16384 x 1024 and 65536 x 256 (lanes along axis 1), in the same run, in alternating blocks:
+d32 (real arrays under a DctHandler: nddct_filter, n real weights; two_calls is nddct2 then nddct3) and the shapes 4096 x 4096, 16384 x 1024 and 65536 x 256 (lanes along axis 1;
+--axis 0: a shape R x C means lanes of R points along axis 0 of an R x C array, the strided axis), in the same run, in alternating blocks:
   two_calls   ndfft then ndifft (real: ndfft_r2c then ndifft_r2c) through a work array: code the filter does not touch, and a lower bound for any three-call
               form (the multiply is left out)
   composed    the filter with fuse=False: the forward transform into the spectrum image, the diagonal pass in place, the inverse
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--min-input-mib", type=int, default=768)
     ap.add_argument("--shapes", default="4096x4096,16384x1024,65536x256")
+    ap.add_argument("--axis", type=int, choices=(0, 1), default=1, help="the axis of the lanes: 1 = rows x n (unit stride), 0 = n x columns (strided)")
     ap.add_argument("--dtypes", default="c128,c64", help="of c128, c64 (complex arrays), f64, f32 (real arrays, R2C) and d64, d32 (real arrays, DCT)")
     args = ap.parse_args()
 
@@ -44,7 +46,10 @@ def main():
         cdt, rdt, rnp = (torch.complex128, torch.float64, np.float64) if dname in ("c128", "f64", "d64") else (torch.complex64, torch.float32, np.float32)
         adt = rdt if real else cdt
         for sh in args.shapes.split(","):
-            rows, n = (int(v) for v in sh.split("x"))
+            dims = tuple(int(v) for v in sh.split("x"))
+            axis = args.axis
+            n = dims[axis]
+            rows = dims[1 - axis]
             nbytes = rows * n * torch.empty((), dtype=adt).element_size()
             npairs = max(2, -(-(args.min_input_mib << 20) // nbytes))
             h = DctHandler(n, rnp) if dct else R2cFftHandler(n, rnp) if real else FftHandler(n, rnp)
@@ -55,25 +60,26 @@ def main():
                 w = torch.from_numpy((rng.uniform(0.5, 2.0, m) * np.exp(2j * np.pi * rng.uniform(0, 1, m))).astype(np.complex128 if rnp is np.float64 else np.complex64)).to("cuda")
             pairs = []
             for _ in range(npairs):
-                x = torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5
+                x = torch.rand(dims, dtype=rdt, device="cuda") - 0.5
                 if not real:
-                    x = torch.complex(x, torch.rand((rows, n), dtype=rdt, device="cuda") - 0.5)
-                pairs.append((x, torch.zeros((rows, n), dtype=adt, device="cuda"), torch.zeros((rows, m), dtype=rdt if dct else cdt, device="cuda")))
+                    x = torch.complex(x, torch.rand(dims, dtype=rdt, device="cuda") - 0.5)
+                wdims = tuple(m if d == axis else e for d, e in enumerate(dims))
+                pairs.append((x, torch.zeros(dims, dtype=adt, device="cuda"), torch.zeros(wdims, dtype=rdt if dct else cdt, device="cuda")))
             k = [0]
 
             def two_calls(x, y, work):
                 if dct:
-                    nddct2(x, work, h, 1); nddct3(work, y, h, 1)
+                    nddct2(x, work, h, axis); nddct3(work, y, h, axis)
                 elif real:
-                    ndfft_r2c(x, work, h, 1); ndifft_r2c(work, y, h, 1)
+                    ndfft_r2c(x, work, h, axis); ndifft_r2c(work, y, h, axis)
                 else:
-                    ndfft(x, work, h, 1); ndifft(work, y, h, 1)
+                    ndfft(x, work, h, axis); ndifft(work, y, h, axis)
 
             def composed(x, y, work):
-                (nddct_filter if dct else ndfft_filter)(x, y, h, 1, w, fuse=False)
+                (nddct_filter if dct else ndfft_filter)(x, y, h, axis, w, fuse=False)
 
             def fused(x, y, work):
-                (nddct_filter if dct else ndfft_filter)(x, y, h, 1, w)
+                (nddct_filter if dct else ndfft_filter)(x, y, h, axis, w)
             forms = {"two_calls": two_calls, "composed": composed, "fused": fused}
             routes = {}
 
@@ -93,7 +99,9 @@ def main():
             for _ in range(args.blocks):
                 for name, fn in forms.items():
                     times[name].append(block(fn, args.steps))
-            rec = {"dtype": dname, "shape": [rows, n], "pairs": npairs, "array_bytes": nbytes, "routes": routes}
+            rec = {"dtype": dname, "shape": list(dims), "pairs": npairs, "array_bytes": nbytes, "routes": routes}
+            if axis != 1:
+                rec["axis"] = axis
             for name in forms:
                 med = float(np.median(times[name]))
                 rec[name + "_us"] = round(med, 2); rec[name + "_us_blocks"] = [round(t, 2) for t in times[name]]
