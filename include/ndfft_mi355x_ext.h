@@ -33,7 +33,9 @@ extern "C" {
  * forward ops the weights are ignored and may be NULL; for every other op a NULL d_weights is NDFFT_ERR_INVALID_ARG.
  * C2R and DCT-I..IV weight the caller's input into a scratch image kept per host thread and stream (allocated by the first call of a
  * size: warm a shape up before capturing it into a HIP graph, as for every multi-pass route); C2C inverse weights the output view in
- * place, after the transform, and writes nothing outside it.  ndfft_last_path() reports "weights+<route>" / "<route>+weights". */
+ * place, after the transform, and writes nothing outside it.  ndfft_last_path() reports "weights+<route>" / "<route>+weights".
+ * A captured graph holds the scratch pointers of its (host thread, stream): a later larger multi-pass call by that thread on that stream,
+ * ndfft_release_workspace and the thread's exit free them, and after any of the three the graph must be captured again (docs/streams.md). */
 int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in, void *d_out, int ndim,
                                const int64_t *shape_in, const int64_t *stride_in,
                                const int64_t *shape_out, const int64_t *stride_out,
@@ -72,7 +74,8 @@ int ndfft_exec_weighted_device(const ndfft_plan *plan, int op, const void *d_in,
  *                                      warm-up call is enough before a capture into a HIP graph.
  *   "<fwd route>+weights+<inv route>"  everything else, and every call with NDFFT_FILTER_NO_FUSE: forward transform into a dense spectrum image kept per host thread
  *                                      and stream, the diagonal pass in place on it, inverse transform into the output.  As for every multi-pass route the first call
- *                                      of a size allocates: warm a shape up before capturing it. */
+ *                                      of a size allocates: warm a shape up before capturing it -- and capture it again once that (host thread, stream)'s scratch
+ *                                      has been freed: by a later larger multi-pass call of the thread on the stream, ndfft_release_workspace or the thread's exit. */
 #define NDFFT_FILTER_NO_FUSE 1   /* take the composed route even where a fused kernel exists (tests, A-B timing) */
 int ndfft_exec_filter_device(const ndfft_plan *plan, const void *d_in, void *d_out, int ndim,
                              const int64_t *shape, const int64_t *stride_in, const int64_t *stride_out, int axis,

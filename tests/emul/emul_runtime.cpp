@@ -56,6 +56,7 @@ void check_guards(const char *when) {
 }
 }  // namespace
 hipError_t hipMalloc(void **p, size_t n) {
+    emul_log_count(EMUL_N_MALLOC);
     char *raw = (char *)malloc(n + 2 * kGuard);
     if (!raw) return 2;
     memset(raw, 0xC3, kGuard); memset(raw + kGuard + n, 0xC3, kGuard);
@@ -67,6 +68,7 @@ hipError_t hipMalloc(void **p, size_t n) {
 }
 hipError_t hipFree(void *p) {
     if (!p) return 0;
+    emul_log_count(EMUL_N_FREE);
     check_guards("hipFree");
     std::lock_guard<std::mutex> g(g_alloc_mu);
     g_allocs.erase((char *)p);
@@ -104,7 +106,8 @@ hipError_t hipDeviceEnablePeerAccess(int peer, unsigned) {
     on = true;
     return 0;
 }
-hipError_t hipMemcpyPeerAsync(void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t) {
+hipError_t hipMemcpyPeerAsync(void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t st) {
+    emul_log_stream(EMUL_ON_MEMCPY_ASYNC, st);
     if (dst_dev != src_dev) {
         std::lock_guard<std::mutex> g(g_peer_mu);
         if (!g_peer[{dst_dev, src_dev}] || !g_peer[{src_dev, dst_dev}]) {
@@ -162,6 +165,29 @@ void emul_count_copy(const void *d, const void *s, hipMemcpyKind k, bool async) 
 }
 extern "C" void emul_copy_counts(long long *out, int reset) {
     for (int i = 0; i < 5; ++i) { if (out) out[i] = g_copies[i].load(); if (reset) g_copies[i] = 0; }
+}
+// test hook: the calling thread's call log since its last reset (hip/hip_runtime.h: EMUL_ON_*, EMUL_N_*).  Copies the stream handle and the kind of the first
+// `cap` stream-ordered calls into streams[] / kinds[] and the EMUL_N_COUNTERS counters into counts[]; returns how many stream-ordered calls were made (the log keeps
+// the first kLogMax of them).  Nothing here is ever destroyed: plans are freed from Python finalisers after the thread's other thread_local objects.
+namespace {
+struct CallLog { std::vector<std::pair<int, void *>> calls; long long total = 0; long long counts[EMUL_N_COUNTERS] = {}; };
+constexpr size_t kLogMax = 1 << 16;
+thread_local CallLog *t_log = nullptr;
+CallLog &call_log() { if (!t_log) t_log = new CallLog; return *t_log; }
+}  // namespace
+void emul_log_stream(int what, hipStream_t s) {
+    CallLog &l = call_log();
+    if (l.calls.size() < kLogMax) l.calls.emplace_back(what, (void *)s);
+    ++l.total;
+}
+void emul_log_count(int which) { ++call_log().counts[which]; }
+extern "C" long long emul_call_log(void **streams, int *kinds, int cap, long long *counts, int reset) {
+    CallLog &l = call_log();
+    const long long total = l.total;
+    for (size_t i = 0; i < l.calls.size() && (long long)i < cap; ++i) { if (kinds) kinds[i] = l.calls[i].first; if (streams) streams[i] = l.calls[i].second; }
+    if (counts) for (int i = 0; i < EMUL_N_COUNTERS; ++i) counts[i] = l.counts[i];
+    if (reset) { l.calls.clear(); l.total = 0; for (auto &c : l.counts) c = 0; }
+    return total;
 }
 extern "C" int emul_is_registered(const void *p) { return emul_host_registered(p) ? 1 : 0; }
 extern "C" size_t emul_host_registered_bytes() {

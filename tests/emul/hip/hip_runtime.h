@@ -54,14 +54,24 @@ hipError_t hipFree(void *p);
 // staging buffer of device 0 showing up while device 1 is current is exactly the bug class this catches
 void emul_check_current(const void *devptr, const char *what);
 void emul_count_copy(const void *d, const void *s, hipMemcpyKind k, bool async);   // emul_runtime.cpp: test counters of host <-> device copies
+// the call log of one host thread (emul_runtime.cpp: emul_call_log; tests/stream_suite.py): the stream handle of every stream-ordered call -- kernel launches (the
+// module launches of jit_stub.cpp come through hipLaunchKernelGGL too), asynchronous copies and fills, event records and waits -- and how often the thread allocated,
+// freed, copied or filled synchronously, or waited.  The emulation never dereferences a stream, so a test may pass any non-null handle and read it back here.
+enum { EMUL_ON_LAUNCH = 0, EMUL_ON_MEMCPY_ASYNC = 1, EMUL_ON_MEMSET_ASYNC = 2, EMUL_ON_EVENT_RECORD = 3, EMUL_ON_WAIT_EVENT = 4 };
+enum { EMUL_N_MALLOC = 0, EMUL_N_FREE = 1, EMUL_N_HOST_MALLOC = 2, EMUL_N_MEMCPY = 3, EMUL_N_MEMSET = 4, EMUL_N_STREAM_SYNC = 5, EMUL_N_DEVICE_SYNC = 6,
+       EMUL_N_EVENT_SYNC = 7, EMUL_N_COUNTERS = 8 };
+void emul_log_stream(int what, hipStream_t s);
+void emul_log_count(int which);
 inline hipError_t emul_memcpy(void *d, const void *s, size_t n, hipMemcpyKind k) {
     if (k == hipMemcpyHostToDevice) emul_check_current(d, "hipMemcpy H2D");
     if (k == hipMemcpyDeviceToHost) emul_check_current(s, "hipMemcpy D2H");
     memcpy(d, s, n); return 0;
 }
-inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { emul_count_copy(d, s, k, false); return emul_memcpy(d, s, n, k); }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
-inline hipError_t hipDeviceSynchronize() { return 0; }
+inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { emul_log_count(EMUL_N_MEMCPY); emul_count_copy(d, s, k, false); return emul_memcpy(d, s, n, k); }
+inline hipError_t hipMemset(void *d, int v, size_t n) { emul_log_count(EMUL_N_MEMSET); memset(d, v, n); return 0; }
+inline hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t s) { emul_log_stream(EMUL_ON_MEMSET_ASYNC, s); memset(d, v, n); return 0; }
+inline hipError_t hipStreamSynchronize(hipStream_t) { emul_log_count(EMUL_N_STREAM_SYNC); return 0; }
+inline hipError_t hipDeviceSynchronize() { emul_log_count(EMUL_N_DEVICE_SYNC); return 0; }
 // pinned-host pipeline of ndfft_exec: never taken in the emulation (no pointer is ever "pinned"), stubs only
 typedef void *hipEvent_t;
 enum { hipEventDisableTiming = 2, hipHostMallocDefault = 0, hipMemoryTypeHost = 1 };
@@ -77,9 +87,9 @@ inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t *a, const void *
 }
 inline hipError_t hipStreamCreate(hipStream_t *s) { *s = nullptr; return 0; }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = nullptr; return 0; }
-inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
+inline hipError_t hipEventRecord(hipEvent_t, hipStream_t s) { emul_log_stream(EMUL_ON_EVENT_RECORD, s); return 0; }
 inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
-inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
+inline hipError_t hipEventSynchronize(hipEvent_t) { emul_log_count(EMUL_N_EVENT_SYNC); return 0; }
 inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
 // peer copies check that each pointer lies in an allocation made on the device it is claimed to be on
 hipError_t hipMemcpyPeerAsync(void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t);
@@ -89,14 +99,15 @@ int emul_device_of(const void *p);   // device an address was hipMalloc'd on, -1
 enum { hipErrorPeerAccessAlreadyEnabled = 704 };
 hipError_t hipDeviceCanAccessPeer(int *can, int dev, int peer);
 hipError_t hipDeviceEnablePeerAccess(int peer, unsigned flags);
-inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
+inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t, unsigned) { emul_log_stream(EMUL_ON_WAIT_EVENT, s); return 0; }
 bool emul_copy_should_fail(const void *a, const void *b);   // emul_runtime.cpp: injected failures of copies on registered host ranges
-inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t) {
+inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t st) {
+    emul_log_stream(EMUL_ON_MEMCPY_ASYNC, st);
     emul_count_copy(d, s, k, true);            // (a copy that is made to fail was still issued: it counts)
     if (emul_copy_should_fail(d, s)) return 1;
     return emul_memcpy(d, s, n, k);
 }
-inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
+inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { emul_log_count(EMUL_N_HOST_MALLOC); *p = malloc(n ? n : 1); return *p ? 0 : 2; }
 inline hipError_t hipHostFree(void *p) { free(p); return 0; }
 enum { hipHostRegisterDefault = 0 };
 // registrations are tracked (emul_runtime.cpp) so that the registration cache of ndfft_exec and the pinned pipeline behind it run on the CPU container;
@@ -122,7 +133,8 @@ void launch(void (*fn)(void *), void *arg, dim3 grid, dim3 block, size_t lds_byt
 #include <tuple>
 #include <utility>
 template <typename... KA, typename... A>
-inline void hipLaunchKernelGGL(void (*k)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t, A... a) {
+inline void hipLaunchKernelGGL(void (*k)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... a) {
+    emul_log_stream(EMUL_ON_LAUNCH, st);
     struct Pack { void (*k)(KA...); std::tuple<typename std::decay<KA>::type...> args; };
     Pack p{k, std::tuple<typename std::decay<KA>::type...>(a...)};
     emul::launch([](void *q) { Pack *s = (Pack *)q; std::apply(s->k, s->args); }, &p, grid, block, lds);
