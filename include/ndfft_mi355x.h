@@ -30,9 +30,10 @@ extern "C" {
 /* Minor revision: bumped when entry points are ADDED (existing ones keep their meaning).  1 = round-4 exports (ndfft_reload_switches,
  * ndfft_documented_switches, ndfft_set_input_hint ...); 2 = ndfft_abi_minor itself; 3 = ndfft_jit_prebuild (round 6); 4 = the entry
  * points of ndfft_mi355x_ext.h (Normalization::Weights on device arrays); 5 = ndfft_exec_filter_device there; 6 =
- * ndfft_exec_dct_filter_device there.  Entry points added
+ * ndfft_exec_dct_filter_device there; 7 = ndfft_last_input_keep, ndfft_set_keep_budget and
+ * ndfft_force_input_keep in ndfft_mi355x_keep.h, which ndfft_mi355x_ext.h includes.  Entry points added
  * from minor 4 on are declared in ndfft_mi355x_ext.h, which includes this header. */
-#define NDFFT_ABI_MINOR 6
+#define NDFFT_ABI_MINOR 7
 
 typedef enum {
     NDFFT_OK = 0,

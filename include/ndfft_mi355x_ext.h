@@ -1,6 +1,6 @@
 /*
  * ndfft_mi355x_ext.h -- entry points added to libndfft_mi355x.so after the core header was frozen for its C99 consumers
- * (ABI minor 4: the weighted call; minor 5: the filter; minor 6: the DCT filter).  C99; includes ndfft_mi355x.h.
+ * (ABI minor 4: the weighted call; minor 5: the filter; minor 6: the DCT filter; minor 7: the kept share of a streamed input, in ndfft_mi355x_keep.h).  C99; includes ndfft_mi355x.h.
  *
  * Normalization::Weights(w): a DIAGONAL normalisation -- a different factor per element of the lane (orthonormal DCT
  * scalings, DCT-I end-point factors, spectral filters, de-aliasing masks).  Unlike Normalization::Custom(fn), a host
@@ -108,4 +108,8 @@ int ndfft_exec_dct_filter_device(const ndfft_plan *plan, const void *d_in, void 
 #ifdef __cplusplus
 }
 #endif
+
+/* ABI minor 7: ndfft_last_input_keep, ndfft_set_keep_budget, ndfft_force_input_keep -- declared in a header of their own */
+#include "ndfft_mi355x_keep.h"
+
 #endif /* NDFFT_MI355X_EXT_H */

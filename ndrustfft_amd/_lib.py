@@ -34,6 +34,8 @@ FILTER_SYMBOLS = ["ndfft_exec_filter_device"]
 FILTER_NO_FUSE = 1
 # ... ABI minor 6: nddct_filter
 DCT_FILTER_SYMBOLS = ["ndfft_exec_dct_filter_device"]
+# ... ABI minor 7: the kept share of a streamed input (include/ndfft_mi355x_keep.h; tests/test_keep_abi.py keeps the two lists identical)
+KEEP_SYMBOLS = ["ndfft_last_input_keep", "ndfft_set_keep_budget", "ndfft_force_input_keep"]
 
 
 _loaded = []          # every Library this process has opened (tests/conftest.py reloads their switches between tests)
@@ -116,6 +118,13 @@ class Library:
         except AttributeError:      # a side build older than ABI minor 6 (see above): nddct_filter on device tensors raises there
             if not os.environ.get("NDFFT_MI355X_LIB"):
                 raise
+        try:
+            L.ndfft_last_input_keep.argtypes = []; L.ndfft_last_input_keep.restype = i32
+            L.ndfft_set_keep_budget.argtypes = [i32]; L.ndfft_set_keep_budget.restype = i32
+            L.ndfft_force_input_keep.argtypes = [i32]; L.ndfft_force_input_keep.restype = i32
+        except AttributeError:      # a side build older than ABI minor 7 (see above): last_input_keep() answers 0 there, the two setters raise
+            if not os.environ.get("NDFFT_MI355X_LIB"):
+                raise
 
     def check(self, status):
         if status == OK:
@@ -146,6 +155,19 @@ class Library:
     def last_input_policy(self):
         """Load policy of the last device exec on this thread: 0 default, 1 streaming loads, -1 fixed by the kernel (diagnostic)."""
         return int(self.c.ndfft_last_input_policy())
+
+    def last_input_keep(self):
+        """Kept share of the last device exec on this thread, 0 .. 64: that many of every 64 blocks of a streamed input were loaded with the default
+        cache policy (diagnostic; 0 on a library older than ABI minor 7)."""
+        return int(self.c.ndfft_last_input_keep()) if hasattr(self.c, "ndfft_last_input_keep") else 0
+
+    def set_keep_budget(self, mib):
+        """Infinity-Cache budget (MiB) of the kept shares, for this thread: 0 = off, negative = the library's default."""
+        self.check(self.c.ndfft_set_keep_budget(mib))
+
+    def force_input_keep(self, keep64):
+        """Test / sweep hook, for this thread: every streamed dense C2C row input keeps keep64 of every 64 blocks; negative = the model decides."""
+        self.check(self.c.ndfft_force_input_keep(keep64))
 
     def explain_plan(self, kind, dtype, n):
         """Text description of the recipes a handler of (kind, dtype, n) would use (diagnostic; needs no GPU)."""

@@ -240,18 +240,35 @@ int current_ws(DeviceWs **out) {
 }
 static thread_local int g_input_hint = NDFFT_INPUT_AUTO;
 static thread_local int g_last_policy = -1;       // load policy the last call on this thread asked the model for (diagnostic)
-void reset_last_policy() { g_last_policy = -1; }
+static thread_local int g_last_keep = 0;          // ... and the kept share (Pow2Args::keep64) it was given (diagnostic)
+static thread_local int g_keep_budget_mb = -1;    // ndfft_set_keep_budget: MiB, -1 = MallModel::kKeepBudget
+static thread_local int g_keep_force = -1;        // ndfft_force_input_keep: 0 .. 64, -1 = the model's share
+void reset_last_policy() { g_last_policy = -1; g_last_keep = 0; }
 static bool F_nt_ok(int F) { return F >= 64; }   // (short lanes: the staging loads are not 16-byte vectors on every path)
 // load policy for the dense C2C row kernels on input `in` (Pow2Args::stream_in), and the bookkeeping for the next call (the model: exec_internal.h, MallModel)
-static int row_load_policy(const void *in, size_t bytes, const void *out, size_t out_bytes);
-int c2c_row_load_policy(const void *in, const void *out, size_t bytes) { return row_load_policy(in, bytes, out, bytes); }
-static int row_load_policy(const void *in, size_t bytes, const void *out, size_t out_bytes) {
+// keep64 (the pow2 row kernel only): where the model grants the input a kept share (MallModel), that share; the other callers stream everything they stream
+// (grant = false: the caller's kernel takes a forced share only -- c64 rows, where the model's share measured slower: DESIGN.md section 3.1)
+static int row_load_policy(const void *in, size_t bytes, const void *out, size_t out_bytes, int *keep64 = nullptr, bool grant = true);
+int c2c_row_load_policy(const void *in, const void *out, size_t bytes, int *keep64, bool grant) { return row_load_policy(in, bytes, out, bytes, keep64, grant); }
+static int row_load_policy(const void *in, size_t bytes, const void *out, size_t out_bytes, int *keep64, bool grant) {
     const int force = sw().stream_loads;            // NDFFT_STREAM_LOADS: 0 / 1 forces a policy
     DeviceWs *ws;
     if (current_ws(&ws)) return -1;
+    const bool model = force < 0 && g_input_hint == NDFFT_INPUT_AUTO;
     int pol = force >= 0 ? (force != 0) : g_input_hint == NDFFT_INPUT_CACHED ? 0 : g_input_hint == NDFFT_INPUT_COLD ? 1 : ws->mall.decide(in, bytes);
     const bool nt = pol >= 0 ? pol != 0 : stream_loads_for(bytes);
     g_last_policy = nt ? 1 : 0;
+    if (keep64) {
+        // the model's own "streaming", or its size-rule path for a buffer it knows (there the share is reported whatever the size rule says: with plain loads
+        // every lane allocates anyway); NDFFT_KEEP64 forces the share of whatever streams
+        // (per host thread, like the hint: ndfft_set_keep_budget / ndfft_force_input_keep; the developer build reads NDFFT_KEEP_BUDGET_MB / NDFFT_KEEP64 for sweeps)
+        const int kb = g_keep_budget_mb >= 0 ? g_keep_budget_mb : (int)NDFFT_DEV_INT("NDFFT_KEEP_BUDGET_MB", -1);
+        const int kf = g_keep_force >= 0 ? g_keep_force : (int)std::min<long>(64, NDFFT_DEV_INT("NDFFT_KEEP64", -1));
+        const uint64_t budget = kb >= 0 ? (uint64_t)kb << 20 : MallModel::kKeepBudget;
+        int k = grant && model && pol != 0 && budget ? ws->mall.share(in, bytes, budget) : 0;
+        if (kf >= 0 && nt) k = kf;
+        *keep64 = g_last_keep = k;
+    }
     ws->mall.note_read(in, bytes);
     // nt stores: a large output bypasses the cache (fft -> ifft on 4096 x 4096 c128: the second pass is 3-5 % faster with streaming loads); a small
     // one is still found there (1024 x 4096, 64 MiB: plain loads 2-3 % faster) -- tools/probes/chain_hint.py, profiles/r05/r05d_chain_hint.txt
@@ -896,7 +913,7 @@ static bool pow2_rows_eligible(const Call &k) { return k.plan->kind == NDFFT_KIN
 static int route_pow2_rows(const Call &k) {
     if (!pow2_rows_eligible(k)) return kDeclined;
     Pow2Args a = c2c_row_args(k);
-    if (k.L.dense) a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)k.P.nlanes * k.plan->n * 2 * real_size(k.plan->dtype));
+    if (k.L.dense) a.stream_in = c2c_row_load_policy(k.in, k.out, (size_t)k.P.nlanes * k.plan->n * 2 * real_size(k.plan->dtype), &a.keep64, k.plan->dtype == NDFFT_F64);
     set_last_path("pow2_reg");
     return launch_pow2(k.plan->dtype, k.n, a, k.stream);
 }
@@ -1134,6 +1151,19 @@ int ndfft_exec_device(const ndfft_plan *plan, int op, const void *d_in, void *d_
 }
 
 int ndfft_last_input_policy(void) { return g_last_policy; }
+int ndfft_last_input_keep(void) { return g_last_keep; }
+int ndfft_set_keep_budget(int mib) {
+    clear_err();
+    if (mib > (1 << 20)) return fail(NDFFT_ERR_INVALID_ARG, "keep budget beyond 2^20 MiB");
+    g_keep_budget_mb = mib < 0 ? -1 : mib;
+    return NDFFT_OK;
+}
+int ndfft_force_input_keep(int keep64) {
+    clear_err();
+    if (keep64 > 64) return fail(NDFFT_ERR_INVALID_ARG, "kept share beyond 64");
+    g_keep_force = keep64 < 0 ? -1 : keep64;
+    return NDFFT_OK;
+}
 
 int ndfft_set_input_hint(int hint) {
     clear_err();

@@ -39,7 +39,8 @@ int prefixed(const char *prefix, int rc);
 // scratch array `which` (DeviceWs::scratch) of this thread on stream s, at least `bytes` long
 int get_scratch(int which, hipStream_t s, size_t bytes, void **out);
 // load policy of a dense row kernel that reads `bytes` at `in` and writes as many at `out` (Pow2Args::stream_in), and the model's bookkeeping for the next call
-int c2c_row_load_policy(const void *in, const void *out, size_t bytes);
+// keep64: the pow2 row kernel's kept share of a streamed input (Pow2Args::keep64; MallModel below) -- callers whose kernel streams everything pass none
+int c2c_row_load_policy(const void *in, const void *out, size_t bytes, int *keep64 = nullptr, bool grant = true);
 void reset_last_policy();         // every entry point, first thing: ndfft_last_input_policy answers for this call
 
 // The lane layout of one call: lane L = (o, i) with i the fastest batch dimension, element j of it at o * outer + i * lane + j * elem.
@@ -121,16 +122,40 @@ struct Pipe {
 //   * a buffer this thread WROTE as an output of more than 64 MiB is cold (nt stores) -> streaming loads when it becomes an input;
 //   * a buffer it READ before (with either policy), or wrote as a small output, is worth plain loads iff the bytes this thread has moved
 //     through the cache since (all inputs, small outputs) plus its own size fit ~256 MiB: a re-read input then is, or becomes, resident;
-//     six rotating 256 MiB inputs never are (streaming loads for all of them);
+//     six rotating 256 MiB inputs never are (streaming loads for all of them, each with a kept share: below);
 //   * a buffer the model has never seen keeps round 2's size rule (plain loads up to 384 MiB) -- its producer is unknown.
 // A stale entry (the allocator reused the addresses for something a foreign kernel produced) costs one call: after that the buffer is "read".
 // ndfft_set_input_hint overrides the model per host thread.  Speed only: either policy gives the same results.
+//
+// The kept share.  LRU is the wrong policy for a CYCLE larger than the cache: it answers a rotation of inputs with "streaming loads for all of them", nothing
+// allocates and the cache sits idle.  Pinning a fixed subset gives a hit rate of cache / footprint instead of 0, and software can pin, because streaming (nt)
+// accesses do not allocate and plain loads do.  So a dense row-kernel input that the model STREAMS and has seen being READ before -- its reuse distance D = the
+// bytes moved through the cache since its last read plus its own size, the quantity decide() forms, exceeds the cache; or it is larger than the cache, the size-rule
+// path -- gets keep64 = floor(64 kKeepBudget / D), at most 63: that many of every 64 blocks of 64 KiB (device_common.h: keep_block, a fixed, evenly spread,
+// nested choice) are loaded with the default policy.  Every member of a rotation then keeps budget / D of itself, kKeepBudget in all, and finds it resident the next
+// time round.  The share is 0 for a buffer last written past the cache (OUT_COLD), an unknown buffer, NDFFT_INPUT_COLD (the caller says the data is not there) and a
+// policy forced by NDFFT_STREAM_LOADS.  The clock still counts every input byte read, kept or not: conservative.  Worst case: kept lanes that miss (a foreign
+// producer rewrote the buffers; the first cycle after the grant) cost what plain loads cost on a cold input, 6 % of their share.
+// c128 rows only: c64 rows of 8192 points (BASELINE configs[2], second transform: three rotating 268 MB inputs) ran 95.7 / 96.7 -> 99.2 / 97.6 us with the model's share of
+// 15, so f32 plans are granted none.  ndfft_set_keep_budget sets the budget per host thread (0: the feature is off), ndfft_force_input_keep forces the share of every
+// streamed dense input, f32 included (tests, sweeps; the developer build reads NDFFT_KEEP_BUDGET_MB / NDFFT_KEEP64).
 struct MallModel {
     enum State { READ = 0, OUT_SMALL = 1, OUT_COLD = 2 };
     struct Entry { uintptr_t lo, hi; uint64_t stamp; int state; };
     std::vector<Entry> e;
     uint64_t clock = 0;                          // bytes this thread has moved through the cache's address stream (inputs read, small outputs)
     static constexpr uint64_t kCap = (uint64_t)256 << 20, kSmallOut = (uint64_t)64 << 20;
+    // what the kept shares of the members of a rotation add up to.  Swept on the six rotating 4096 x 4096 c128 pairs (profiles/r16/budget_sweep.txt):
+    // 0 / 96 / 144 / 192 / 216 / 240 / 288 / 384 MiB kept -> 90.5 / 89.2 / 88.8 / 87.6 / 87.7 / 88.7 / 89.7 / 89.8 us; 216 MiB is still at the best time and the
+    // next step is not, so the budget stays one step below it
+    static constexpr uint64_t kKeepBudget = (uint64_t)192 << 20;
+    // kept share (Pow2Args::keep64) of input `in`, which decide() did not answer with plain loads; before note_read
+    int share(const void *in, size_t bytes, uint64_t budget) {
+        const Entry *x = find(in, bytes);
+        if (!x || x->state != READ || bytes == 0) return 0;
+        const uint64_t d = clock - x->stamp + bytes;
+        return (int)std::min<uint64_t>(63, 64 * budget / d);
+    }
     Entry *find(const void *p, size_t bytes) {
         const uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
         for (auto &x : e) if (lo < x.hi && x.lo < hi) return &x;

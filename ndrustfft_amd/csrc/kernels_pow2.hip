@@ -85,6 +85,11 @@ template <typename T, int N, int NT, int VEC, int FL, int PS> static int launch_
     if (nblk > 0x7fffffffLL) return fail(NDFFT_ERR_UNSUPPORTED, "too many lanes for one launch");
     Pow2Args a = a0;
     a.xcd_chunk = xcd_chunk_for((size_t)LPB * N * sizeof(cpx<T>), nblk);
+    // the kept share counts blocks of 64 KiB of a DENSE input (a lane of that size or more is its own block); a pitched one keeps nothing
+    constexpr size_t lane_bytes = (size_t)N * sizeof(cpx<T>);
+    a.keep_shift = 0;
+    for (size_t b = lane_bytes; b < ((size_t)64 << 10); b <<= 1) ++a.keep_shift;
+    if ((NT & 4) == 0) a.keep64 = 0;
     // developer knob (A/B only): extra dynamic LDS per workgroup = fewer resident workgroups per CU
     const size_t pad = (size_t)NDFFT_DEV_INT("NDFFT_POW2_LDS_PAD_KB", 0) << 10;
     hipLaunchKernelGGL(k_pow2<K>, dim3((unsigned)nblk), dim3(K::THREADS), std::min(K::LDS_BYTES + pad, (size_t)160 * 1024), s, a);
@@ -103,6 +108,10 @@ template <typename T, int N, int NT, int VEC, int FL = 0> static int launch_inst
 template <typename T, int N, int NT, int VEC, int FL = 0> static int launch_one(const Pow2Args &a, hipStream_t s) {
     static_assert(NT == 1, "callers name the store policy; the load policy is chosen here");
     const bool nt_in = a.stream_in >= 0 ? a.stream_in != 0 : stream_loads_for((size_t)a.nlanes * N * sizeof(cpx<T>));
+    // a kept share (Pow2Args::keep64, dense inputs) runs the instance that carries the per-lane choice; everything else the one it always ran
+    if constexpr (FL == 0) {
+        if (nt_in && a.keep64 > 0 && a.pitch_in == N) return launch_inst<T, N, 7, VEC, FL>(a, s);
+    }
     if (nt_in) return launch_inst<T, N, 3, VEC, FL>(a, s);
     return launch_inst<T, N, 1, VEC, FL>(a, s);
 }

@@ -662,8 +662,7 @@ const Switches *parse_switches() {
     S->rfs_c2r_tile = on("NDFFT_RFS_C2R_TILE", true);
     S->rfs_logn1 = (int)num("NDFFT_RFS_LOGN1", 0, 0, 11);
     S->cs_chunk_mb = (int)num("NDFFT_CS_CHUNK_MB", 144, 0, 1 << 20);
-    S->stream_loads = (int)num("NDFFT_STREAM_LOADS", -1, -1, 1);
-    if (const char *e = getenv("NDFFT_HOST_PIPE")) S->host_pipe = e[0] == '1' ? 1 : e[0] == '0' ? 0 : -1;
+    S->stream_loads = (int)num("NDFFT_STREAM_LOADS", -1, -1, 1);    if (const char *e = getenv("NDFFT_HOST_PIPE")) S->host_pipe = e[0] == '1' ? 1 : e[0] == '0' ? 0 : -1;
     S->host_reg_cache_mb = num("NDFFT_HOST_REG_CACHE_MB", 0, 0, 1L << 22);
     S->copy_threads = (int)num("NDFFT_COPY_THREADS", 0, 0, 64);
     S->shard_chunk_kb = num("NDFFT_SHARD_CHUNK_KB", 0, 1, 1L << 24);

@@ -77,7 +77,7 @@ template <typename T, bool NT> __device__ __forceinline__ void gstore(cpx<T> *p,
 //   64 = (with 32) the latency form with DERIVED powers: a radix-8 / 16 pass loads W^k, W^2k, W^4k (, W^8k) only -- the rows bit 4 reads -- and builds the other powers after
 //        the exchange, so 3 (4) complex registers wait across it instead of R - 1; run() issues pass 1's loads right behind the data loads, pass p + 1's follow pass p's
 //        twiddle multiplies.  The loads are pinned there (tw_load) -- as plain loads the compiler sinks them back behind the exchange.  Row kernel only (run()).
-// NT: bit 0 = non-temporal stores, bit 1 = non-temporal loads
+// NT: bit 0 = non-temporal stores, bit 1 = non-temporal loads, bit 2 (with bit 1, row kernel only) = a kept share of the lanes loads with the default policy (Pow2Args::keep64)
 // VEC = 2 (f32 only): global loads/stores move TWO adjacent complex elements (16 B) per lane; the
 //   first and last pass then own adjacent butterfly pairs j = 2t, 2t+1 instead of j = t, t+TPL.
 //   Needs E/R >= 2 in those passes, even lane pitches and 16-byte aligned bases (checked on the host).
@@ -297,6 +297,28 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
         }
     }
 
+    // the first pass's inputs x[j + r N / R0] of the lane at `in`, straight from global memory; NTL: with the streaming policy
+    template <bool NTL> static __device__ __forceinline__ void load_lane(cpx<T> (&v)[E], const cpx<T> *in, int t) {
+        constexpr int R0 = RL::at(0), NB0 = N / R0, NBF0 = slots(0);
+        if constexpr (VEC == 2) {
+            static_assert(NBF0 % 2 == 0 && full(0) && full(RL::NP - 1), "VEC=2 needs an even number of whole butterfly rounds in the first and last pass");
+#pragma unroll
+            for (int q = 0; q < NBF0; q += 2)
+#pragma unroll
+                for (int r = 0; r < R0; ++r) {
+                    const vec4f w = gload4<NTL>((const float *)(in + jof<0>(t, q) + r * NB0));
+                    v[q * R0 + r] = mk<T>(w.x, w.y); v[(q + 1) * R0 + r] = mk<T>(w.z, w.w);
+                }
+        } else {
+#pragma unroll
+            for (int q = 0; q < NBF0; ++q)
+                if (full(0) || t + q * TPL < NB0) {
+#pragma unroll
+                    for (int r = 0; r < R0; ++r) v[q * R0 + r] = gload<T, NTL>(in + t + q * TPL + r * NB0);
+                }
+        }
+    }
+
     static __device__ __forceinline__ void run(const Pow2Args &a) {
         extern __shared__ __attribute__((aligned(16))) char smem[];
         const int t = threadIdx.x % TPL, ll = threadIdx.x / TPL;
@@ -306,25 +328,14 @@ template <typename T, int N, int TPL, int LPB, bool HALF, typename RL, int FLAGS
         cpx<T> *out = (cpx<T> *)a.out + (live ? lane : 0) * a.pitch_out;
         char *lds = smem + (size_t)ll * LANE_LDS * (HALF ? sizeof(T) : 2 * sizeof(T));
         cpx<T> v[E];
-        {
-            constexpr int R0 = RL::at(0), NB0 = N / R0, NBF0 = slots(0);
-            if constexpr (VEC == 2) {
-                static_assert(NBF0 % 2 == 0 && full(0) && full(RL::NP - 1), "VEC=2 needs an even number of whole butterfly rounds in the first and last pass");
-#pragma unroll
-                for (int q = 0; q < NBF0; q += 2)
-#pragma unroll
-                    for (int r = 0; r < R0; ++r) {
-                        const vec4f w = gload4<(NT & 2) != 0>((const float *)(in + jof<0>(t, q) + r * NB0));
-                        v[q * R0 + r] = mk<T>(w.x, w.y); v[(q + 1) * R0 + r] = mk<T>(w.z, w.w);
-                    }
-            } else {
-#pragma unroll
-                for (int q = 0; q < NBF0; ++q)
-                    if (full(0) || t + q * TPL < NB0) {
-#pragma unroll
-                        for (int r = 0; r < R0; ++r) v[q * R0 + r] = gload<T, (NT & 2) != 0>(in + t + q * TPL + r * NB0);
-                    }
-            }
+        // NT bit 2, the streaming-load instances with a kept share: the kept blocks of the input (Pow2Args::keep64) take the default policy.  Per lane: uniform over
+        // the workgroup at LPB = 1.  An instance of its own: the branch cost c64 n = 8192 rows 1 % where nothing is kept
+        if constexpr ((NT & 4) != 0) {
+            static_assert((NT & 2) != 0, "a kept share is a form of the streaming-load instances");
+            if (keep_block(lane, a.keep64, a.keep_shift)) load_lane<false>(v, in, t);
+            else load_lane<true>(v, in, t);
+        } else {
+            load_lane<(NT & 2) != 0>(v, in, t);
         }
         // derived latency form: pass 1's power rows right behind the data loads -- vmcnt counts in order, so the wait for the data leaves them in flight
         cpx<T> w[DERIVE ? E : 1];
