@@ -48,10 +48,10 @@ def strides_of(v):
     return [s // v.itemsize for s in v.strides]
 
 
-def dev_call(L, h, name, xa, xv, ya, yv, axis, w=None, *, weighted=True, norm=_lib.NORM_NONE, n_weights=None, w_offset=0, check=True):
+def dev_call(L, h, name, xa, xv, ya, yv, axis, w=None, *, weighted=True, norm=_lib.NORM_NONE, scale=0.0, n_weights=None, w_offset=0, check=True):
     """One call on device images of the allocations xa / ya (C-contiguous host arrays), the views xv / yv into them giving the geometry.  weighted:
     ndfft_exec_weighted_device with weights w (None: NULL; w_offset: the vector starts that many elements into its allocation), else ndfft_exec_device
-    with `norm`.  Returns (image of the output allocation after the call, last path, status)."""
+    with (`norm`, `scale`).  Returns (image of the output allocation after the call, last path, status)."""
     din, dout = DevBuf(L, xa), DevBuf(L, ya)
     dw = None
     try:
@@ -65,7 +65,7 @@ def dev_call(L, h, name, xa, xv, ya, yv, axis, w=None, *, weighted=True, norm=_l
                 wp = ctypes.c_void_p(dw.p.value + w_offset * w.itemsize)
             st = L.c.ndfft_exec_weighted_device(*args, wp, (len(w) if w is not None else 0) if n_weights is None else n_weights, None)
         else:
-            st = L.c.ndfft_exec_device(*args, norm, 0.0, None)
+            st = L.c.ndfft_exec_device(*args, norm, scale, None)
         LAST["msg"] = L.c.ndfft_last_error().decode()      # (the calls below clear it)
         if check:
             L.check(st)
